@@ -15,6 +15,9 @@ before anything in this process touches a GPU) and relays rank 0's line; it refu
 visible.  `--rehearse` replaces the GPU step by a sleep so that the launch / reduce / report path runs on a CPU-only
 box (tests/test_sharding_gloo.py).
 
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0) as DIR/<name>.npy after the run, so that two
+builds can be compared output for output: the inputs are seeded and the same from run to run for the same arguments.
+
 Extra objects in that line:
   roofline     -- for the slower of the two kernels: algorithmic bytes per launch
                   (15 B/px x the pixels of the frames that launch covers: 3 u8 in + 12 f32 out
@@ -49,6 +52,42 @@ CONFIGS = {
     "c3": dict(rows=2160, cols=3840, sigma=50.0, frames=8, label="C3: 3840x2160 RGB u8, sigma=50"),
     "c5": dict(rows=4320, cols=7680, sigma=20.0, frames=1, label="C5: fastboxblur 7680x4320 RGB u8, 3 passes, k=41"),
 }
+
+# --dump-outputs: what the timed path computed in its last step, at most DUMP_BYTES of .npy data; an output too large to write whole
+# is written as a fixed seeded sample of DUMP_SAMPLE values (the same indices on every run of the same shape)
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22
+DUMP_SEED = 0x5EED00D5
+
+
+def output_snapshot(name, t):
+    """host arrays (float32 / float64) of one u8 output t, [frames,] rows, cols, 3, on the device: `name` (the whole output, when it
+    fits), or `name`_sample at seeded flat indices `name`_sample_index with the first frame's top-left 256 x 256 `name`_corner; always
+    `name`_sums, the sum of every (frame, channel) plane over all of its pixels"""
+    import numpy as np
+    import torch
+    f = t if t.dim() == 4 else t.unsqueeze(0)
+    res = {name + "_sums": f.sum(dim=(1, 2), dtype=torch.float64).cpu().numpy()}
+    n = t.numel()
+    if 4 * n + res[name + "_sums"].nbytes <= DUMP_BYTES:
+        res[name] = t.cpu().numpy().astype(np.float32)
+        return res
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    res[name + "_sample"] = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy().astype(np.float32)
+    res[name + "_sample_index"] = idx.astype(np.float64)
+    res[name + "_corner"] = f[0, :256, :256].cpu().numpy().astype(np.float32)
+    return res
+
+
+def write_dump(dirpath, arrays):
+    """DIR/<name>.npy for every array of output_snapshot()"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_BYTES))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def native_oracle():
@@ -197,8 +236,9 @@ def copy_bandwidth(ctx, mib=1024, reps=5):
     return ctx.copy_bandwidth(mib, reps)
 
 
-def box_leg(ctx, torch, dev, steps, warmup, copy=False):
-    """BASELINE config 5: fastboxblur (call site Source.cpp:587), 8K RGB u8, box width 41, 3 passes, in place, device-resident"""
+def box_leg(ctx, torch, dev, steps, warmup, copy=False, dump=None):
+    """BASELINE config 5: fastboxblur (call site Source.cpp:587), 8K RGB u8, box width 41, 3 passes, in place, device-resident;
+    dump (a dict): gets output_snapshot() of the image after the last step"""
     c = CONFIGS["c5"]
     rows, cols, k, passes = c["rows"], c["cols"], 41, 3
     g = torch.Generator(device=dev)
@@ -221,6 +261,8 @@ def box_leg(ctx, torch, dev, steps, warmup, copy=False):
         marks[i + 1].record()
     torch.cuda.synchronize(dev)
     per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)]
+    if dump is not None:
+        dump.update(output_snapshot("fastboxblur_out", img))
     px = rows * cols
     ms = 1e3 * dt / steps
     # The kernels as built move the image twice (all horizontal sweeps in one launch, all vertical ones in another): 12 B/px, and that
@@ -246,7 +288,11 @@ def box_config(args, torch, B):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     ctx = B.BlurContext(0)
-    print(json.dumps(box_leg(ctx, torch, dev, args.steps, args.warmup, copy=not args.no_copy)), flush=True)
+    dump = {} if args.dump_outputs else None
+    rec = box_leg(ctx, torch, dev, args.steps, args.warmup, copy=not args.no_copy, dump=dump)
+    if dump:
+        write_dump(args.dump_outputs, dump)
+    print(json.dumps(rec), flush=True)
 
 
 def reference_sweep(args, torch, B):
@@ -501,7 +547,14 @@ def main():
                     help="reference-sweep: the reference's own benchmark (Source.cpp:627-635): 45 RGB images 1000x1500 ... 7600x11400, "
                          "sigma = sqrt(longer side), one image per call; prints one JSON line with a row per size")
     ap.add_argument("--rehearse", action="store_true", help="no GPU work: the step is a sleep (launch / reduce / report path on a CPU-only box)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy, float32 / "
+                         "float64, at most 64 MB: the whole output or a fixed seeded sample of it, per-plane sums and a corner crop")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.rehearse or args.preset):
+        raise SystemExit("--dump-outputs writes what the timed GPU path computed: not with --rehearse or --preset")
     cfg = CONFIGS[args.config]
     for k in ("rows", "cols", "sigma", "frames"):
         if getattr(args, k) is None:
@@ -595,6 +648,8 @@ def main():
     if two_regions:
         inst_elapsed, tm, per_step = run.timed(step, args.steps, 0, 1, step_events=not args.no_step_events)
         instrumented_ms = 1e3 * inst_elapsed / args.steps
+    # `out` holds the last timed step's frames until the legs below reuse it
+    snapshot = output_snapshot("pffft_out", out) if args.dump_outputs and rank == 0 else None
     family = ctx.last_family()
     natural = None
     if args.data == "synthetic" and not args.no_natural:
@@ -689,6 +744,8 @@ def main():
             rec["configs"] = configs
         if world == 1 and not args.no_cpu:
             rec["cpu_baseline"] = cpu_baseline(rows, cols, sigma)
+        if snapshot:
+            write_dump(args.dump_outputs, snapshot)
         print(json.dumps(rec), flush=True)
 
     if world > 1:

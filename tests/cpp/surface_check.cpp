@@ -1,14 +1,18 @@
 // surface_check.cpp -- a "user of the reference" written against include/blur_amd.hpp with the
 // reference's global names.  Modes:
-//   host                                       host-side functions only (no GPU), self-checking
+//   host [dir]                                 host-side functions only (no GPU), self-checking; scratch files
+//                                              go to dir (default $TMPDIR or /tmp, one name per process)
 //   blur in.raw rows cols sigma out.raw        pffft_(cv::Mat-like&, sigma) on the GPU
 //   box  in.raw w h ch ksize passes out.raw    fastboxblur(...) on the GPU
 #define BLUR_AMD_GLOBAL_NAMES
 #include "blur_amd.hpp"
 
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <iterator>
+#include <string>
+#include <unistd.h>
 
 struct FakeMat {               // the three members pffft_() uses of cv::Mat (Source.cpp:434,459-461)
     unsigned char* data;
@@ -23,7 +27,7 @@ static std::vector<uint8_t> slurp(const char* p)
 
 #define REQUIRE(c) do { if (!(c)) { std::printf("FAILED: %s (line %d)\n", #c, __LINE__); return 1; } } while (0)
 
-static int host_checks()
+static int host_checks(const std::string& dir)
 {
     REQUIRE(gaussian_window(5) == 31 && gaussian_window(20) == 131 && gaussian_window(50) == 331);
     REQUIRE(gaussian_window(200, 1024) == 1025);
@@ -80,7 +84,7 @@ static int host_checks()
         im.pixels.resize(5 * 7 * 3);
         for (size_t i = 0; i < im.pixels.size(); ++i) im.pixels[i] = (uint8_t)(i * 37 + 11);
         im.data = im.pixels.data();
-        const std::string path = "/tmp/blur_amd_surface_check.ppm";
+        const std::string path = dir + "/blur_amd_surface_check_" + std::to_string((long)getpid()) + ".ppm";
         REQUIRE(imwrite(path, im));
         Image back2 = imread(path);
         REQUIRE(back2.size[0] == 5 && back2.size[1] == 7 && back2.pixels == im.pixels && back2.data == back2.pixels.data());
@@ -89,6 +93,7 @@ static int host_checks()
         std::fwrite(im.pixels.data(), 1, im.pixels.size(), f);
         std::fclose(f);
         Image back3 = imread(path);
+        std::remove(path.c_str());
         REQUIRE(back3.pixels == im.pixels && back3.channels() == 3);
         REQUIRE(imread("/nonexistent/file.ppm").empty());
     }
@@ -100,7 +105,10 @@ int main(int argc, char** argv)
 {
     const std::string mode = argc > 1 ? argv[1] : "host";
     try {
-        if (mode == "host") return host_checks();
+        if (mode == "host") {
+            const char* tmp = std::getenv("TMPDIR");
+            return host_checks(argc > 2 ? argv[2] : (tmp && *tmp ? tmp : "/tmp"));
+        }
         if (mode == "blur" && argc == 7) {
             std::vector<uint8_t> img = slurp(argv[2]);
             FakeMat m{ img.data(), { std::atoi(argv[3]), std::atoi(argv[4]) } };
@@ -136,6 +144,6 @@ int main(int argc, char** argv)
         std::printf("error: %s\n", e.what());
         return 3;
     }
-    std::printf("usage: surface_check host | blur in rows cols sigma out | box in w h ch ksize passes out\n");
+    std::printf("usage: surface_check host [dir] | blur in rows cols sigma out | box in w h ch ksize passes out\n");
     return 2;
 }

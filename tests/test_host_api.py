@@ -121,15 +121,15 @@ def test_pffft_include_path_shim(tmp_path):
 
 
 @pytest.mark.parametrize("mode", [["-fopenmp"], ["-DMYLOOP", "-pthread"], []])
-def test_cpp_header_with_reference_names(mode):
+def test_cpp_header_with_reference_names(mode, tmp_path):
     """include/blur_amd.hpp under the reference's three hybrid_loop build modes (Utils.hpp:24-54): OpenMP, -DMYLOOP
     (std::thread blocks: the published build, .vscode/tasks.json:21) and serial"""
-    exe = os.path.join(ROOT, "tests", "cpp", "surface_check")
+    exe = str(tmp_path / "surface_check")
     subprocess.check_call(["g++", "-std=c++17", "-O1"] + mode + ["-I" + os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "cpp", "surface_check.cpp"),
                            "-L" + os.path.dirname(B.LIB_PATH), "-lblur_amd", "-Wl,-rpath," + os.path.dirname(B.LIB_PATH),
                            "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    out = subprocess.run([exe, "host"], capture_output=True, text=True)
+    out = subprocess.run([exe, "host", str(tmp_path)], capture_output=True, text=True)
     assert out.returncode == 0 and "host ok" in out.stdout, out.stdout + out.stderr
 
 

@@ -42,5 +42,5 @@ def test_cpp_surface_host_half_under_asan_ubsan(tmp_path, mode):
     exe = _build(tmp_path, "surface_check_san",
                  [os.path.join(ROOT, "tests", "cpp", "surface_check.cpp"), os.path.join(ROOT, "tests", "cpp", "host_abi_for_sanitizers.cpp"),
                   os.path.join(ROOT, "blur_algorithms_amd", "csrc", "host_math.cpp")], flags=mode)
-    out = subprocess.run([exe, "host"], capture_output=True, text=True, env=ENV, timeout=600)
+    out = subprocess.run([exe, "host", str(tmp_path)], capture_output=True, text=True, env=ENV, timeout=600)
     assert out.returncode == 0 and "host ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
