@@ -86,6 +86,23 @@ def boxfft_sizing(rows, cols, nsmooth):
     return dict(kLen=out[0], pad=out[1], N0=out[2], N1=out[3])
 
 
+def fastboxblur_batch_plan(nframes, w, h, channels, ksize, passes):
+    """how blur_fastboxblur_u8_batch_dev runs a batch (host only, no GPU):
+    (frames_per_chunk, chunks, vertical_on_matrix_cores, horizontal_on_matrix_cores)"""
+    out = (C.c_int * 4)()
+    rc = _L().blur_fastboxblur_batch_plan(int(nframes), int(w), int(h), int(channels), int(ksize), int(passes), out)
+    if rc:
+        raise BlurError(rc, "fastboxblur_batch_plan: bad arguments")
+    return tuple(out)
+
+
+def _box_frames_shape(shape):
+    """[n, h, w] or [n, h, w, C] -> (n, w, h, C)"""
+    if len(shape) not in (3, 4):
+        raise ValueError("expected uint8 frames [n, h, w] or [n, h, w, C]")
+    return shape[0], shape[2], shape[1], 1 if len(shape) == 3 else shape[3]
+
+
 def fft_plan_radices(n):
     r = (C.c_int * 16)()
     k = _L().blur_fft_plan_radices(int(n), r)
@@ -430,6 +447,24 @@ class BlurContext:
         self._check(self._lib.blur_fastboxblur_u8_dev(self._h, image.data_ptr(), w, h, ch, int(ksize), int(passes)))
         return image
 
+    def fastboxblur_batch(self, frames, ksize, passes):
+        """fastboxblur of every frame of a batch: frames uint8 [n, h, w] or [n, h, w, C].  A contiguous torch CUDA tensor is blurred
+        in place on torch's current stream (blur_fastboxblur_u8_batch_dev) and returned; a numpy array goes through the host
+        batch entry and the blurred copy is returned."""
+        if isinstance(frames, np.ndarray):
+            a = np.array(frames, np.uint8, order="C")
+            n, w, h, ch = _box_frames_shape(a.shape)
+            self._check(self._lib.blur_fastboxblur_u8_host_batch(self._h, a.ctypes.data, n, w, h, ch, int(ksize), int(passes)))
+            return a
+        import torch
+        t = frames
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("expected a contiguous CUDA uint8 tensor [n, h, w] or [n, h, w, C]")
+        n, w, h, ch = _box_frames_shape(tuple(t.shape))
+        self.use_torch_stream()
+        self._check(self._lib.blur_fastboxblur_u8_batch_dev(self._h, t.data_ptr(), n, w, h, ch, int(ksize), int(passes)))
+        return t
+
 
 class BlurMulti:
     """Several GPUs (or several logical shards on one GPU) behind one handle: blur_multi_* of include/blur_amd.h.
@@ -483,3 +518,19 @@ class BlurMulti:
                                                                  float(sigma), C.byref(o)))
         return dst
 
+    def fastboxblur(self, frames, ksize, passes):
+        """fastboxblur of every frame: frames uint8 [n, h, w] or [n, h, w, C]; a torch CUDA tensor on devices[0] (blurred in place
+        and returned) or a numpy array in host memory (the blurred copy is returned).  Synchronous."""
+        if isinstance(frames, np.ndarray):
+            a = np.array(frames, np.uint8, order="C")
+            n, w, h, ch = _box_frames_shape(a.shape)
+            self._check(self._lib.blur_fastboxblur_u8_batch_multi_host(self._h, a.ctypes.data, n, w, h, ch, int(ksize), int(passes)))
+            return a
+        import torch
+        t = frames
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.device.index != self.devices[0]:
+            raise ValueError("expected a contiguous CUDA uint8 tensor [n, h, w] or [n, h, w, C] on devices[0]")
+        n, w, h, ch = _box_frames_shape(tuple(t.shape))
+        torch.cuda.synchronize(t.device)
+        self._check(self._lib.blur_fastboxblur_u8_batch_multi_dev(self._h, t.data_ptr(), n, w, h, ch, int(ksize), int(passes)))
+        return t

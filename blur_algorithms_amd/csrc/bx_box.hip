@@ -100,9 +100,12 @@ template <int NB> __device__ __forceinline__ v4i bx_band(int u, int m, int q, in
 // P DELTA rows above the segment and the first P (W - 1) steps only fill the pipeline.  (Skewing the sweeps by one step each, so
 // that the P products of an iteration are independent of each other, changed nothing in the horizontal kernel and cost 12 % in
 // this one: the chain is hidden by the other waves already.)
+// Frames: a batch of frames of h rows each, back to back, is walked frame by frame: the wave id is (frame, segment, strip), strip
+// fastest, and the wave's buffer resources cover its own frame only (base = the frame, size = h pitch), so the row reflection
+// happens at the frame's own top and bottom and no load or store can reach a neighbouring frame.
 template <int NB, int P, int NT>
 __global__ __launch_bounds__(256) void bx_vert_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int h, int pitch, int r, int s_band, uint32_t mul,
-                                                      int seg_rows, int nstrips, int nwaves)
+                                                      int seg_rows, int nstrips, int nseg, int nwaves)
 {
     constexpr int W = 4 * NB, DELTA = 32 * NB - 8, FILL = P * (W - 1);
     static_assert(NT % 4 == 0, "dwordx4 loads");
@@ -112,14 +115,15 @@ __global__ __launch_bounds__(256) void bx_vert_kernel(const uint8_t* __restrict_
     // (Walking every other segment of a strip upwards, so that two neighbours read the P DELTA rows either side of their boundary at
     // the same time, with or without the four segments of a strip in one workgroup, was measured at 8K: 53.5 and 69 us against 52 --
     // the re-read rows do not cost memory bandwidth, and four adjacent strips per workgroup, 256 contiguous bytes of a row, matter.)
-    const int strip = wid % nstrips, seg = wid / nstrips;
+    const int strip = wid % nstrips, fs = wid / nstrips, frame = fs / nseg, seg = fs - frame * nseg;
     const int ys = seg * seg_rows, ye = min(h, ys + seg_rows);
     const int S = FILL + (ye - ys + 15) / 16, R0 = ys - P * DELTA;
     const uint32_t col0 = static_cast<uint32_t>(strip) * (16 * NT) + 4 * NT * qd;
     const uint32_t sel1 = (l & 1) ? 0x03070105u : 0x06020400u, sel2 = (l & 2) ? 0x03020706u : 0x05040100u;
     const uint32_t bytes = static_cast<uint32_t>(h) * static_cast<uint32_t>(pitch);
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(in), 0, bytes, kRsrcWord3);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, bytes, kRsrcWord3);
+    const size_t fbase = static_cast<size_t>(frame) * bytes;
+    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(in) + fbase, 0, bytes, kRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out + fbase, 0, bytes, kRsrcWord3);
     const bool whole16 = (pitch & 15) == 0;
 
     v4i band[W];
@@ -226,33 +230,35 @@ bool bx_constants(int r, int* s_band, uint32_t* mul)
 }
 
 template <int NB, int P, int NT>
-hipError_t bx_launch_vert(hipStream_t st, const uint8_t* in, uint8_t* out, int h, int pitch, int r, int s_band, uint32_t mul, int num_cus)
+hipError_t bx_launch_vert(hipStream_t st, const uint8_t* in, uint8_t* out, int nframes, int h, int pitch, int r, int s_band, uint32_t mul, int num_cus)
 {
     constexpr int W = 4 * NB;
     const int nstrips = (pitch + 16 * NT - 1) / (16 * NT);
     // segments: four waves per SIMD in all (measured at 8K, k = 41, P = 3: 82 / 62 / 53 / 54 / 64 us with 3 / 6 / 10 / 14 / 30 segments
     // of 360 strips -- the walk is a chain of dependent matrix and vector instructions and lives on other waves' work), but no
-    // segment shorter than twice the rows it takes to fill its pipeline
+    // segment shorter than twice the rows it takes to fill its pipeline.  The count is over the whole batch (nframes nstrips
+    // columns of strips): many frames give whole-column walks, which pay the pipeline fill once per column
     const int fill_rows = 16 * P * (W - 1);
-    int nseg = (16 * num_cus + nstrips / 2) / nstrips;
+    const long long cols = static_cast<long long>(nframes) * nstrips;
+    int nseg = static_cast<int>((16ll * num_cus + cols / 2) / cols);
     const int most = h / (2 * fill_rows);
     if (nseg > most) nseg = most;
     if (bx_env("BLUR_BX_VSEG") > 0) nseg = bx_env("BLUR_BX_VSEG");
     if (nseg < 1) nseg = 1;
     int seg_rows = ((h + nseg - 1) / nseg + 15) / 16 * 16;
     nseg = (h + seg_rows - 1) / seg_rows;
-    const int nwaves = nstrips * nseg;
-    hipLaunchKernelGGL((bx_vert_kernel<NB, P, NT>), dim3((nwaves + 3) / 4), dim3(256), 0, st, in, out, h, pitch, r, s_band, mul, seg_rows, nstrips, nwaves);
+    const int nwaves = nframes * nstrips * nseg;
+    hipLaunchKernelGGL((bx_vert_kernel<NB, P, NT>), dim3((nwaves + 3) / 4), dim3(256), 0, st, in, out, h, pitch, r, s_band, mul, seg_rows, nstrips, nseg, nwaves);
     return hipGetLastError();
 }
 
 template <int NB, int NT>
-hipError_t bx_launch_vert_p(hipStream_t st, const uint8_t* in, uint8_t* out, int h, int pitch, int r, int passes, int s_band, uint32_t mul, int num_cus)
+hipError_t bx_launch_vert_p(hipStream_t st, const uint8_t* in, uint8_t* out, int nframes, int h, int pitch, int r, int passes, int s_band, uint32_t mul, int num_cus)
 {
     switch (passes) {
-    case 1: return bx_launch_vert<NB, 1, NT>(st, in, out, h, pitch, r, s_band, mul, num_cus);
-    case 2: return bx_launch_vert<NB, 2, NT>(st, in, out, h, pitch, r, s_band, mul, num_cus);
-    default: return bx_launch_vert<NB, 3, NT>(st, in, out, h, pitch, r, s_band, mul, num_cus);
+    case 1: return bx_launch_vert<NB, 1, NT>(st, in, out, nframes, h, pitch, r, s_band, mul, num_cus);
+    case 2: return bx_launch_vert<NB, 2, NT>(st, in, out, nframes, h, pitch, r, s_band, mul, num_cus);
+    default: return bx_launch_vert<NB, 3, NT>(st, in, out, nframes, h, pitch, r, s_band, mul, num_cus);
     }
 }
 
@@ -681,22 +687,30 @@ bool bx_horz_geom(int h, int w, int C, int r, int passes, BxHorzGeom* g)
 
 }  // namespace
 
-hipError_t bx_vertical(hipStream_t st, const uint8_t* in, uint8_t* out, int h, int pitch, int r, int passes, int num_cus, bool* ran)
+bool bx_vertical_applies(int h, int pitch, int r, int passes)
+{
+    int s_band = 0;
+    uint32_t mul = 0;
+    if (passes < 1 || passes > 3 || !bx_constants(r, &s_band, &mul)) return false;
+    const int nb = r <= 24 ? 1 : r <= 56 ? 2 : 0;
+    if (!nb) return false;
+    const int delta = 32 * nb - 8;
+    return !(pitch & 3) && h >= passes * delta + 32 && static_cast<long long>(h) * pitch < (1ll << 31);
+}
+
+hipError_t bx_vertical(hipStream_t st, const uint8_t* in, uint8_t* out, int nframes, int h, int pitch, int r, int passes, int num_cus, bool* ran)
 {
     *ran = false;
     int s_band = 0;
     uint32_t mul = 0;
-    if (passes < 1 || passes > 3 || !bx_constants(r, &s_band, &mul)) return hipSuccess;
-    const int nb = r <= 24 ? 1 : r <= 56 ? 2 : 0;
-    if (!nb) return hipSuccess;
-    const int delta = 32 * nb - 8;
-    if ((pitch & 3) || (reinterpret_cast<uintptr_t>(in) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return hipSuccess;
-    if (h < passes * delta + 32 || static_cast<long long>(h) * pitch >= (1ll << 31)) return hipSuccess;
+    if (nframes < 1 || !bx_vertical_applies(h, pitch, r, passes) || !bx_constants(r, &s_band, &mul)) return hipSuccess;
+    if ((reinterpret_cast<uintptr_t>(in) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return hipSuccess;
     *ran = true;
-    // narrow images: 64-byte strips give twice the waves
-    const bool narrow = bx_env("BLUR_BX_VNT") ? bx_env("BLUR_BX_VNT") == 4 : pitch < 128 * 2 * num_cus;
-    if (nb == 1) return narrow ? bx_launch_vert_p<1, 4>(st, in, out, h, pitch, r, passes, s_band, mul, num_cus) : bx_launch_vert_p<1, 8>(st, in, out, h, pitch, r, passes, s_band, mul, num_cus);
-    return narrow ? bx_launch_vert_p<2, 4>(st, in, out, h, pitch, r, passes, s_band, mul, num_cus) : bx_launch_vert_p<2, 8>(st, in, out, h, pitch, r, passes, s_band, mul, num_cus);
+    const int nb = r <= 24 ? 1 : 2;
+    // narrow images (batches: all frames' columns together): 64-byte strips give twice the waves
+    const bool narrow = bx_env("BLUR_BX_VNT") ? bx_env("BLUR_BX_VNT") == 4 : static_cast<long long>(nframes) * pitch < 128ll * 2 * num_cus;
+    if (nb == 1) return narrow ? bx_launch_vert_p<1, 4>(st, in, out, nframes, h, pitch, r, passes, s_band, mul, num_cus) : bx_launch_vert_p<1, 8>(st, in, out, nframes, h, pitch, r, passes, s_band, mul, num_cus);
+    return narrow ? bx_launch_vert_p<2, 4>(st, in, out, nframes, h, pitch, r, passes, s_band, mul, num_cus) : bx_launch_vert_p<2, 8>(st, in, out, nframes, h, pitch, r, passes, s_band, mul, num_cus);
 }
 
 size_t bx_horizontal_scratch(int h, int w, int C, int r, int passes)
@@ -705,6 +719,14 @@ size_t bx_horizontal_scratch(int h, int w, int C, int r, int passes)
     if (bx_horz3_geom(h, w, C, r, passes, &g)) return 64;          // (the channel-plane kernel needs none)
     if (!bx_horz_geom(h, w, C, r, passes, &g)) return 0;
     return static_cast<size_t>(h) * g.mpitch + 64;
+}
+
+bool bx_horizontal_applies(int h, int w, int C, int r, int passes)
+{
+    int s_band = 0;
+    uint32_t mul = 0;
+    BxHorzGeom g;
+    return bx_constants(r, &s_band, &mul) && (bx_horz3_geom(h, w, C, r, passes, &g) || bx_horz_geom(h, w, C, r, passes, &g));
 }
 
 hipError_t bx_horizontal(hipStream_t st, const uint8_t* in, uint8_t* out, uint8_t* margins, int h, int w, int C, int r, int passes, int num_cus, bool* ran)

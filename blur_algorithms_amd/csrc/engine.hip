@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -2613,16 +2614,18 @@ static bool box_no_mfma()
     return off;
 }
 
-int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int channels, int ksize, int passes)
+// ---- fastboxblur: one chunk of whole frames, and the plan that cuts a batch into chunks ----------------------------------
+// The horizontal sweeps see a chunk of nframes frames of h rows as one image of nframes h rows (rows are independent); the
+// vertical ones walk frame by frame (bx_vertical's frame dimension; the accumulator fallbacks loop over the frames on the host).
+// A chunk of one frame is exactly the single-image call.
+static int box_run_chunk(blur_ctx* ctx, uint8_t* d_inout, int nframes, int w, int h, int channels, int ksize, int passes)
 {
-    if (!ctx) return BLUR_ERR_INVALID;
-    if (!d_inout || w <= 0 || h <= 0 || channels <= 0 || ksize <= 0 || passes < 0)
-        return fail(ctx, BLUR_ERR_INVALID, "fastboxblur: bad arguments");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = static_cast<size_t>(w) * h * channels;
+    const size_t fbytes = static_cast<size_t>(w) * h * channels;
+    const size_t bytes = fbytes * nframes;
+    const int rows = nframes * h;         // (a chunk's bytes are below 2^31: box_batch_plan)
     // the second image, and behind it the mirrored row margins of the matrix-core horizontal kernel (bx_box.hip)
     const size_t margins_at = (bytes + 255) & ~static_cast<size_t>(255);
-    const size_t margins_bytes = bx_horizontal_scratch(h, w, channels, std::min((ksize - 1) / 2, w - 1), std::min(passes, 3));
+    const size_t margins_bytes = bx_horizontal_scratch(rows, w, channels, std::min((ksize - 1) / 2, w - 1), std::min(passes, 3));
     if (ctx->box_bytes < margins_at + margins_bytes) {
         if (ctx->box_tmp) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); HIP_TRY(ctx, hipFree(ctx->box_tmp)); ctx->box_tmp = nullptr; ctx->box_bytes = 0; }
         HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->box_tmp), margins_at + margins_bytes));
@@ -2630,14 +2633,16 @@ int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int c
     }
     uint8_t *a = d_inout, *b = ctx->box_tmp;
     uint8_t* margins = margins_bytes ? ctx->box_tmp + margins_at : nullptr;
-    auto sweep = [&](int nlines, int n, size_t lstride, size_t xstride) {
+    // one sweep of the accumulator kernel over `frames` frames of `fstride` bytes each (one launch per frame)
+    auto sweep = [&](int nlines, int n, size_t lstride, size_t xstride, int frames, size_t fstride) {
         int r = (ksize - 1) / 2;
         if (r > n - 1) r = n - 1;
         const int seg_len = std::max(64, (n + 31) / 32);
         const int nseg = (n + seg_len - 1) / seg_len;
         const long long items = static_cast<long long>(nlines) * channels * nseg;
         const unsigned grid = static_cast<unsigned>((items + 255) / 256);
-        hipLaunchKernelGGL(boxsweep_kernel, dim3(grid), dim3(256), 0, ctx->stream, a, b, nlines, n, lstride, xstride, channels, r, seg_len);
+        for (int f = 0; f < frames; ++f)
+            hipLaunchKernelGGL(boxsweep_kernel, dim3(grid), dim3(256), 0, ctx->stream, a + fstride * f, b + fstride * f, nlines, n, lstride, xstride, channels, r, seg_len);
         std::swap(a, b);
     };
     // horizontal sweeps: all passes of a row inside LDS when two copies of the row fit
@@ -2653,7 +2658,7 @@ int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int c
         while (hdone < passes) {
             const int now = std::min(3, passes - hdone);
             bool ran = false;
-            HIP_TRY(ctx, bx_horizontal(ctx->stream, a, b, margins, h, w, channels, r_row, now, ctx->num_cus, &ran));
+            HIP_TRY(ctx, bx_horizontal(ctx->stream, a, b, margins, rows, w, channels, r_row, now, ctx->num_cus, &ran));
             if (!ran) break;
             std::swap(a, b);
             hdone += now;
@@ -2667,7 +2672,7 @@ int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int c
         const size_t lds = 2 * static_cast<size_t>(buf_bytes);
         auto launch = [&](auto kern) -> int {
             if (int rc = set_lds(ctx, kern, lds)) return rc;
-            hipLaunchKernelGGL(kern, dim3(h), dim3(256), lds, ctx->stream, a, b, w, r_row, hleft, gpt, off0, buf_bytes);
+            hipLaunchKernelGGL(kern, dim3(rows), dim3(256), lds, ctx->stream, a, b, w, r_row, hleft, gpt, off0, buf_bytes);
             return BLUR_OK;
         };
         int rc = channels == 1 ? launch(boxrow4_kernel<1>) : channels == 3 ? launch(boxrow4_kernel<3>) : launch(boxrow4_kernel<4>);
@@ -2679,10 +2684,10 @@ int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int c
         if (r > w - 1) r = w - 1;
         const int nseg = std::max(1, 256 / channels);
         const int seg_len = (w + nseg - 1) / nseg;
-        hipLaunchKernelGGL(boxrow_kernel, dim3(h), dim3(256), row_lds, ctx->stream, a, b, w, channels, r, hleft, seg_len, nseg);
+        hipLaunchKernelGGL(boxrow_kernel, dim3(rows), dim3(256), row_lds, ctx->stream, a, b, w, channels, r, hleft, seg_len, nseg);
         std::swap(a, b);
     } else {
-        for (int p = 0; p < hleft; ++p) sweep(h, w, static_cast<size_t>(w) * channels, static_cast<size_t>(channels));
+        for (int p = 0; p < hleft; ++p) sweep(rows, w, static_cast<size_t>(w) * channels, static_cast<size_t>(channels), 1, 0);
     }
     // vertical sweeps: up to three at a time in one launch on the integer matrix cores (bx_box.hip) where that kernel applies
     int vdone = 0;
@@ -2692,7 +2697,7 @@ int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int c
         while (vdone < passes && r > 0) {
             const int now = std::min(3, passes - vdone);
             bool ran = false;
-            HIP_TRY(ctx, bx_vertical(ctx->stream, a, b, h, static_cast<int>(static_cast<size_t>(w) * channels), r, now, ctx->num_cus, &ran));
+            HIP_TRY(ctx, bx_vertical(ctx->stream, a, b, nframes, h, static_cast<int>(static_cast<size_t>(w) * channels), r, now, ctx->num_cus, &ran));
             if (!ran) break;
             std::swap(a, b);
             vdone += now;
@@ -2710,15 +2715,113 @@ int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int c
         nseg = (h + seg_len - 1) / seg_len;
         const long long items = static_cast<long long>(pitch4) * nseg;
         for (int p = vdone; p < passes; ++p) {
-            hipLaunchKernelGGL(boxcol4_kernel, dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0, ctx->stream, a, b, h, pitch4, r, seg_len, nseg);
+            for (int f = 0; f < nframes; ++f)
+                hipLaunchKernelGGL(boxcol4_kernel, dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0, ctx->stream, a + fbytes * f, b + fbytes * f, h, pitch4, r, seg_len, nseg);
             std::swap(a, b);
         }
     } else {
-        for (int p = vdone; p < passes; ++p) sweep(w, h, static_cast<size_t>(channels), static_cast<size_t>(w) * channels);
+        for (int p = vdone; p < passes; ++p) sweep(w, h, static_cast<size_t>(channels), static_cast<size_t>(w) * channels, nframes, fbytes);
     }
     HIP_TRY(ctx, hipGetLastError());
     if (a != d_inout) HIP_TRY(ctx, hipMemcpyAsync(d_inout, a, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return BLUR_OK;
+}
+
+// Chunk cap: a chunk's intermediate image (between the horizontal and the vertical kernel) should stay in the 256 MB Infinity
+// Cache.  BLUR_BOX_CHUNK_MIB (developer knob, tools/bx_batch.py sweeps it) overrides it.
+constexpr size_t kBoxChunkCap = 128ull << 20;
+// the rows of one launch of bx_margins_kernel: its grid has one row of blocks per 8 image rows (gridDim.y < 65536)
+constexpr long long kBoxChunkRows = 65535ll * 8;
+
+struct BoxBatchPlan {
+    int frames_per_chunk = 0, chunks = 0;
+    bool vert_mfma = false, horz_mfma = false;    // every sweep of that direction on the integer matrix cores (bx_box.hip)
+};
+
+// argument checks and chunking of a batch (no GPU): false = bad arguments.  Chunks are as many whole frames as fit under the cap
+// and under 2^31 bytes (the 32-bit offsets of the matrix-core kernels) and kBoxChunkRows rows; a frame larger than that is a
+// chunk of its own (the single-image call).
+static bool box_batch_plan(int nframes, int w, int h, int channels, int ksize, int passes, BoxBatchPlan* plan)
+{
+    if (nframes < 0 || w <= 0 || h <= 0 || channels <= 0 || ksize <= 0 || passes < 0) return false;
+    long long pitch = 0, fbytes = 0, total = 0;
+    if (__builtin_mul_overflow(static_cast<long long>(w), channels, &pitch) || pitch > INT32_MAX || __builtin_mul_overflow(pitch, h, &fbytes) ||
+        __builtin_mul_overflow(fbytes, nframes, &total))
+        return false;
+    const char* e = getenv("BLUR_BOX_CHUNK_MIB");
+    const long long cap = e && atoi(e) > 0 ? static_cast<long long>(atoi(e)) << 20 : static_cast<long long>(kBoxChunkCap);
+    long long fpc = std::min({ cap / fbytes, ((1ll << 31) - 1) / fbytes, kBoxChunkRows / h });
+    fpc = std::max(1ll, std::min(fpc, std::max(1ll, static_cast<long long>(nframes))));
+    plan->frames_per_chunk = static_cast<int>(fpc);
+    plan->chunks = static_cast<int>((nframes + fpc - 1) / fpc);
+    // the matrix-core flags: the decline rules of bx_box.hip on the rows of a (full) chunk.  The sweeps go in groups of up to three
+    // and a rule that admits three sweeps admits fewer, so the first group decides
+    const int rows = static_cast<int>(fpc * h), now = std::min(passes, 3);
+    const int rh = std::min((ksize - 1) / 2, w - 1), rv = std::min((ksize - 1) / 2, h - 1);
+    plan->horz_mfma = !box_no_mfma() && passes > 0 && rh > 0 && bx_horizontal_applies(rows, w, channels, rh, now);
+    plan->vert_mfma = !box_no_mfma() && passes > 0 && rv > 0 && bx_vertical_applies(h, static_cast<int>(pitch), rv, now);
+    return true;
+}
+
+int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int channels, int ksize, int passes)
+{
+    if (!ctx) return BLUR_ERR_INVALID;
+    if (!d_inout || w <= 0 || h <= 0 || channels <= 0 || ksize <= 0 || passes < 0)
+        return fail(ctx, BLUR_ERR_INVALID, "fastboxblur: bad arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return box_run_chunk(ctx, d_inout, 1, w, h, channels, ksize, passes);
+}
+
+int blur_fastboxblur_batch_plan(int nframes, int w, int h, int channels, int ksize, int passes, int out[4])
+{
+    BoxBatchPlan p;
+    if (!out || !box_batch_plan(nframes, w, h, channels, ksize, passes, &p)) return BLUR_ERR_INVALID;
+    out[0] = p.frames_per_chunk;
+    out[1] = p.chunks;
+    out[2] = p.vert_mfma ? 1 : 0;
+    out[3] = p.horz_mfma ? 1 : 0;
+    return BLUR_OK;
+}
+
+int blur_fastboxblur_u8_batch_dev(blur_ctx* ctx, uint8_t* d_inout, int nframes, int w, int h, int channels, int ksize, int passes)
+{
+    if (!ctx) return BLUR_ERR_INVALID;
+    BoxBatchPlan p;
+    if (!box_batch_plan(nframes, w, h, channels, ksize, passes, &p) || (nframes > 0 && !d_inout))
+        return fail(ctx, BLUR_ERR_INVALID, "fastboxblur batch: bad arguments");
+    if (nframes == 0) return BLUR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t fbytes = static_cast<size_t>(w) * h * channels;
+    for (int f = 0; f < nframes; f += p.frames_per_chunk)
+        if (int rc = box_run_chunk(ctx, d_inout + fbytes * f, std::min(p.frames_per_chunk, nframes - f), w, h, channels, ksize, passes)) return rc;
+    return BLUR_OK;
+}
+
+int blur_fastboxblur_u8_host_batch(blur_ctx* ctx, uint8_t* inout, int nframes, int w, int h, int channels, int ksize, int passes)
+{
+    if (!ctx) return BLUR_ERR_INVALID;
+    BoxBatchPlan p;
+    if (!box_batch_plan(nframes, w, h, channels, ksize, passes, &p) || (nframes > 0 && !inout))
+        return fail(ctx, BLUR_ERR_INVALID, "fastboxblur batch: bad arguments");
+    if (nframes == 0) return BLUR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t fbytes = static_cast<size_t>(w) * h * channels;
+    void* dv = nullptr;
+    if (int rc0 = ensure_host_stage(ctx, fbytes * p.frames_per_chunk, &dv)) return rc0;
+    uint8_t* d = static_cast<uint8_t*>(dv);
+    // chunk by chunk through the stage: copy in, blur, copy out (stream order keeps the stage's reuse safe)
+    int rc = BLUR_OK;
+    hipError_t e = hipSuccess;
+    for (int f = 0; f < nframes && e == hipSuccess && rc == BLUR_OK; f += p.frames_per_chunk) {
+        const int n = std::min(p.frames_per_chunk, nframes - f);
+        e = hipMemcpyAsync(d, inout + fbytes * f, fbytes * n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) rc = box_run_chunk(ctx, d, n, w, h, channels, ksize, passes);
+        if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(inout + fbytes * f, d, fbytes * n, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { ctx->err = std::string("host fastboxblur batch: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
+    return rc;
 }
 
 int blur_fastboxblur_u8_host(blur_ctx* ctx, uint8_t* inout, int w, int h, int channels, int ksize, int passes)
@@ -2799,14 +2902,14 @@ int blur_multi_shards(const blur_multi* m) { return m ? static_cast<int>(m->ctxs
 const char* blur_multi_last_error(const blur_multi* m) { return m ? m->err.c_str() : "null blur_multi"; }
 
 // location: 0 = src/dst are host pointers (pinned memory overlaps the copies of different shards), 1 = device pointers
-// on devices[0].  Synchronous: returns when every shard is done.
-static int blur_multi_run(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, double sigma,
-                          const blur_opts* opts, int location)
+// on devices[0].  Synchronous: returns when every shard is done.  `fb`: bytes per frame (0: a non-positive size);
+// `body(ctx, in, out, n)` queues the work of one shard's n frames on its context's stream.
+using ShardBody = std::function<int(blur_ctx*, const uint8_t*, uint8_t*, int)>;
+static int blur_multi_run(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, size_t fb, int location, const ShardBody& body)
 {
     if (!m) return BLUR_ERR_INVALID;
-    if (!src || !dst || nframes < 0 || rows <= 0 || cols <= 0) { m->err = "null frame pointer, negative frame count or non-positive size"; return BLUR_ERR_INVALID; }
+    if (!src || !dst || nframes < 0 || fb == 0) { m->err = "null frame pointer, negative frame count or non-positive size"; return BLUR_ERR_INVALID; }
     const int S = static_cast<int>(m->ctxs.size());
-    const size_t fb = static_cast<size_t>(rows) * cols * 3;
     int rc_all = BLUR_OK;
     for (int r = 0; r < S && rc_all == BLUR_OK; ++r) {
         const int b = static_cast<int>(static_cast<long long>(nframes) * r / S), e = static_cast<int>(static_cast<long long>(nframes) * (r + 1) / S);
@@ -2832,7 +2935,7 @@ static int blur_multi_run(blur_multi* m, const uint8_t* src, uint8_t* dst, int n
                                                 : hipMemcpyPeerAsync(work_in, m->devices[r], in, m->devices[0], bytes, st);
             if (er != hipSuccess) { hip_fail(er, "fan-out copy"); break; }
         }
-        const int rc = blur_gaussian_u8c3_batch_dev(c, work_in, work_out, e - b, rows, cols, sigma, opts);
+        const int rc = body(c, work_in, work_out, e - b);
         if (rc != BLUR_OK) { m->err = std::string("shard ") + std::to_string(r) + ": " + blur_last_error(c); rc_all = rc; break; }
         if (!local) {
             const hipError_t er = location == 0 ? hipMemcpyAsync(outp, work_out, bytes, hipMemcpyDeviceToHost, st)
@@ -2848,18 +2951,48 @@ static int blur_multi_run(blur_multi* m, const uint8_t* src, uint8_t* dst, int n
     return rc_all;
 }
 
+static size_t gaussian_frame_bytes(int rows, int cols) { return rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * 3 : 0; }
+static ShardBody gaussian_shard(int rows, int cols, double sigma, const blur_opts* opts)
+{
+    return [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) { return blur_gaussian_u8c3_batch_dev(c, in, out, n, rows, cols, sigma, opts); };
+}
+
 int blur_gaussian_u8c3_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, double sigma, const blur_opts* opts)
 {
     if (m) {
         // frames queued by the caller on devices[0] must be complete before other devices (and other streams) read them
         if (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
     }
-    return blur_multi_run(m, d_src, d_dst, nframes, rows, cols, sigma, opts, 1);
+    return blur_multi_run(m, d_src, d_dst, nframes, gaussian_frame_bytes(rows, cols), 1, gaussian_shard(rows, cols, sigma, opts));
 }
 
 int blur_gaussian_u8c3_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, double sigma, const blur_opts* opts)
 {
-    return blur_multi_run(m, src, dst, nframes, rows, cols, sigma, opts, 0);
+    return blur_multi_run(m, src, dst, nframes, gaussian_frame_bytes(rows, cols), 0, gaussian_shard(rows, cols, sigma, opts));
+}
+
+// fastboxblur: in place, so every shard's input is its output
+static int box_multi(blur_multi* m, uint8_t* inout, int nframes, int w, int h, int channels, int ksize, int passes, int location)
+{
+    if (!m) return BLUR_ERR_INVALID;
+    BoxBatchPlan p;
+    if (!box_batch_plan(nframes, w, h, channels, ksize, passes, &p) || (nframes > 0 && !inout)) { m->err = "fastboxblur batch: bad arguments"; return BLUR_ERR_INVALID; }
+    if (nframes == 0) return BLUR_OK;
+    if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
+    const size_t fb = static_cast<size_t>(w) * h * channels;
+    return blur_multi_run(m, inout, inout, nframes, fb, location, [=](blur_ctx* c, const uint8_t*, uint8_t* out, int n) {
+        return blur_fastboxblur_u8_batch_dev(c, out, n, w, h, channels, ksize, passes);
+    });
+}
+
+int blur_fastboxblur_u8_batch_multi_dev(blur_multi* m, uint8_t* d_inout, int nframes, int w, int h, int channels, int ksize, int passes)
+{
+    return box_multi(m, d_inout, nframes, w, h, channels, ksize, passes, 1);
+}
+
+int blur_fastboxblur_u8_batch_multi_host(blur_multi* m, uint8_t* inout, int nframes, int w, int h, int channels, int ksize, int passes)
+{
+    return box_multi(m, inout, nframes, w, h, channels, ksize, passes, 0);
 }
 
 int blur_convolve_lines_c32_dev(blur_ctx* ctx, const float* d_in, float* d_out, int nlines, int n, const float* multipliers)

@@ -236,6 +236,30 @@ int blur_fastboxblur_u8_dev(blur_ctx* ctx, uint8_t* d_inout, int w, int h, int c
 int blur_fastboxblur_u8_host(blur_ctx* ctx, uint8_t* inout, int w, int h, int channels,
                              int ksize, int passes);
 
+/* fastboxblur over a batch of nframes frames stored back to back (stride w*h*channels bytes), in place; every frame is
+   blurred on its own (reflect-101 at its own borders), byte for byte what nframes single calls give.  The batch runs in
+   chunks of whole frames: as many as fit under 2^31 bytes (the kernels' 32-bit offsets), under 65535*8 rows and under a cap
+   of 128 MiB that keeps the intermediate image between the horizontal and the vertical sweeps in the Infinity Cache (DESIGN.md
+   section 5); a frame larger than that is a chunk of its own.  Per chunk, with passes <= 3 on the integer matrix cores, two
+   launches: horizontal in -> scratch, vertical scratch -> in.  The ctx's scratch is sized per chunk, not per batch.
+   BLUR_ERR_INVALID: nframes < 0, a non-positive w / h / channels / ksize, passes < 0, nframes*w*h*channels overflowing,
+   w*channels above INT_MAX, or a null pointer with nframes > 0.  nframes == 0 is a no-op.
+     ..._batch_dev : DEVICE memory, asynchronous on the ctx's stream;
+     ..._host_batch: HOST memory, synchronous: each chunk is copied in, blurred and copied out through the ctx's staging buffer. */
+int blur_fastboxblur_u8_batch_dev(blur_ctx* ctx, uint8_t* d_inout, int nframes, int w, int h, int channels,
+                                  int ksize, int passes);
+int blur_fastboxblur_u8_host_batch(blur_ctx* ctx, uint8_t* inout, int nframes, int w, int h, int channels,
+                                   int ksize, int passes);
+/* host-only plan of the call above (no GPU needed; the same host code the batch entries use):
+   out = { frames_per_chunk, chunks, vertical_on_matrix_cores (0/1), horizontal_on_matrix_cores (0/1) }.  A flag is 1 when that
+   direction has sweeps to do (passes > 0, a box wider than one pixel after clamping r to w-1 / h-1) and they all run on the
+   matrix cores; 0 means the accumulator kernels.  The vertical kernel declines (per frame) r > 56, w*channels not a multiple of
+   4, h < passes*delta + 32 (delta = 24 for r <= 24, 56 for r <= 56; passes counted up to 3) and frames of 2^31 bytes or more;
+   the horizontal ones decline r > 56 for three channels and channels*r > 120 otherwise, rows under 128 bytes,
+   rows not a multiple of 4 bytes (other than three channels), channel counts other than 1/3/4.  4-byte aligned pointers assumed.
+   BLUR_ERR_INVALID on the arguments the batch entries refuse (or a null `out`). */
+int blur_fastboxblur_batch_plan(int nframes, int w, int h, int channels, int ksize, int passes, int out[4]);
+
 /* ---- several GPUs behind one handle (SURVEY.md 8(b) S1 "ctx owning a device list", 8(e)) -------------------------------
    Frames are independent (Source.cpp:510 runs even the channels serially; the reference's only parallelism is
    hybrid_loop over tiles, Utils.hpp:16-55), so a batch shards by frame with no exchange: shard r of S takes frames
@@ -254,6 +278,12 @@ int blur_gaussian_u8c3_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint
                                        double sigma, const blur_opts* opts);
 int blur_gaussian_u8c3_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols,
                                         double sigma, const blur_opts* opts);
+/* fastboxblur over a batch, sharded by frame exactly like the two calls above, in place (blur_fastboxblur_u8_batch_dev on
+   each shard); arguments and errors as blur_fastboxblur_u8_batch_dev, nframes == 0 is a no-op, shards without frames idle. */
+int blur_fastboxblur_u8_batch_multi_dev(blur_multi* m, uint8_t* d_inout, int nframes, int w, int h, int channels,
+                                        int ksize, int passes);
+int blur_fastboxblur_u8_batch_multi_host(blur_multi* m, uint8_t* inout, int nframes, int w, int h, int channels,
+                                         int ksize, int passes);
 
 /* ---- batched line convolution: what pffft_transform_ordered(FORWARD) -> pffft_sorted_optimized_convolution ->
    pffft_transform_ordered(BACKWARD) (Source.cpp:531-533,553-555) is per tile, for MANY lines at once --------------
