@@ -103,6 +103,21 @@ def _box_frames_shape(shape):
     return shape[0], shape[2], shape[1], 1 if len(shape) == 3 else shape[3]
 
 
+def _gauss_frames_shape(shape):
+    """[rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4} -> (n, rows, cols, C)"""
+    if len(shape) == 2:
+        n, rows, cols, ch = 1, shape[0], shape[1], 1
+    elif len(shape) == 3:
+        n, (rows, cols, ch) = 1, shape
+    elif len(shape) == 4:
+        n, rows, cols, ch = shape
+    else:
+        n = ch = 0
+    if ch not in (1, 3, 4):
+        raise ValueError("expected uint8 [rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4}")
+    return n, rows, cols, ch
+
+
 def fft_plan_radices(n):
     r = (C.c_int * 16)()
     k = _L().blur_fft_plan_radices(int(n), r)
@@ -433,6 +448,38 @@ class BlurContext:
         self._check(self._lib.blur_interleave_bgr_f32_u8_dev(self._h, planes.data_ptr(), out.data_ptr(), total))
         return out
 
+    def gaussian(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
+        """Gaussian blur of a 1-, 3- or 4-channel uint8 image (grayscale, BGR, BGRA / RGBA): [rows, cols], [rows, cols, C] or a batch
+        [n, rows, cols, C], C in {1, 3, 4}.  Every channel, alpha included, is blurred on its own exactly as pffft_ blurs one of
+        its three (blur_gaussian_u8_batch_dev).  engine: None (the library's choice), "fused" or "fft".
+
+        torch CUDA tensor: asynchronous on torch's current stream, returns `out` (default: in place, like pffft_).  numpy array:
+        host round trip, returns a new array.
+        """
+        o = self._opts(nyquist_quirk, engine=engine)
+        if isinstance(image, np.ndarray):
+            a = np.ascontiguousarray(image, np.uint8)
+            n, rows, cols, ch = _gauss_frames_shape(a.shape)
+            res = np.empty_like(a) if out is None else out
+            if res.shape != a.shape or res.dtype != np.uint8 or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must match the input")
+            fb = rows * cols * ch
+            for f in range(n):
+                self._check(self._lib.blur_gaussian_u8_host(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch,
+                                                            float(sigma), C.byref(o)))
+            return res
+        import torch
+        t = image
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("expected a contiguous CUDA uint8 tensor [rows, cols], [rows, cols, C] or [n, rows, cols, C]")
+        n, rows, cols, ch = _gauss_frames_shape(tuple(t.shape))
+        dst = t if out is None else out
+        if dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
+            raise ValueError("out must match the input")
+        self.use_torch_stream()
+        self._check(self._lib.blur_gaussian_u8_batch_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
+        return dst
+
     def fastboxblur(self, image, ksize, passes):
         """fastboxblur(in, w, h, channels, ksize, passes), in place -- call site Source.cpp:587"""
         if isinstance(image, np.ndarray):
@@ -516,6 +563,32 @@ class BlurMulti:
         torch.cuda.synchronize(t.device)
         self._check(self._lib.blur_gaussian_u8c3_batch_multi_dev(self._h, t.data_ptr(), dst.data_ptr(), t.shape[0], t.shape[1], t.shape[2],
                                                                  float(sigma), C.byref(o)))
+        return dst
+
+    def gaussian(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
+        """BlurContext.gaussian over a batch sharded by frame: frames uint8 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
+        tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
+        o = BlurOpts()
+        self._lib.blur_opts_default(C.byref(o))
+        o.nyquist_quirk = 1 if nyquist_quirk else 0
+        if engine is not None:
+            o.engine = ENGINES[engine]
+        if isinstance(frames, np.ndarray):
+            a = np.ascontiguousarray(frames, np.uint8)
+            if a.ndim != 4:
+                raise ValueError("expected uint8 frames [n, rows, cols, C]")
+            n, rows, cols, ch = _gauss_frames_shape(a.shape)
+            res = np.empty_like(a) if out is None else out
+            self._check(self._lib.blur_gaussian_u8_batch_multi_host(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, float(sigma), C.byref(o)))
+            return res
+        import torch
+        t = frames
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.dim() != 4 or t.device.index != self.devices[0]:
+            raise ValueError("expected a contiguous CUDA uint8 tensor [n, rows, cols, C] on devices[0]")
+        n, rows, cols, ch = _gauss_frames_shape(tuple(t.shape))
+        dst = t if out is None else out
+        torch.cuda.synchronize(t.device)
+        self._check(self._lib.blur_gaussian_u8_batch_multi_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
         return dst
 
     def fastboxblur(self, frames, ksize, passes):

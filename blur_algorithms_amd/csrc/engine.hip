@@ -763,6 +763,10 @@ struct blur_ctx {
     float* work2 = nullptr;      // second set of planes: very tall images only (column pass without the LDS pixel stage)
     size_t work2_bytes = 0;
     uint8_t* box_tmp = nullptr;
+    float* ch_planes = nullptr;      // 1- / 4-channel plane fallback: the frame's f32 planes
+    size_t ch_planes_bytes = 0;
+    uint8_t* ch_copy = nullptr;      // 1- / 4-channel images: a copy of overlapping source frames
+    size_t ch_copy_bytes = 0;
     size_t box_bytes = 0;
     std::string engine_note;      // BLUR_ENGINE_AUTO: why the last call's choice passed over a faster engine ("" if it did not)
     int last_family = -1;         // kernels the last u8c3 blur used: 0 run-time plans, 1 specialised rows-first, 2 wave-resident, 3 whole-image 2D, 4 matrix-core (two kernels), 6 fused matrix-core
@@ -1690,6 +1694,194 @@ static int run_colpass_u8c3(blur_ctx* ctx, const float* planes, uint8_t* dst, in
 }
 
 // ======================================================================================
+// 1- and 4-channel u8 images (blur_gaussian_u8_*): every channel blurred on its own as pffft_() blurs one of its three
+// ======================================================================================
+#include "fc_registry.hpp"
+
+static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
+{
+    if (*have >= bytes) return BLUR_OK;
+    if (*buf) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipFree(*buf));
+        *buf = nullptr;
+        *have = 0;
+    }
+    HIP_TRY(ctx, hipMalloc(buf, bytes));
+    *have = bytes;
+    return BLUR_OK;
+}
+
+// the fused kernel for CH = 1, 4 (fc_kernels.hpp): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
+// Frames are disjoint from the destination here (blur_u8_batch_impl copies overlapping ones first).
+static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
+{
+    const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
+    const FcEntry* fe = find_fc_entry(nkb);
+    if (!fe) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for 1 / 4 channels: no kernel instantiated for this pad");
+    FxGeom g{ rows, cols, p.sz.pad, nframes, 0, (rows + 31) / 32, fx_right_strips(cols, pada), ctx->num_xcds };
+    const int chunks_x = (cols + kFxChunk - 1) / kFxChunk, win = kFxChunk + 2 * pada, nstrips = fx_left_strips(pada) + g.nright;
+    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->fx_strips), &ctx->fx_strips_bytes, static_cast<size_t>(nframes) * nstrips * rows * win * ch + 64)) return rc;
+    const int strip_blocks = (rows * (ch * win / 4) + 255) / 256;
+    const int n_strip = strip_blocks * nstrips * nframes;
+    const int G = fc_groups_per_thread(cols, ch), ndw = (cols * ch + 3) / 4, nbatches = (ndw + 256 * G - 1) / (256 * G), cpitch = 4 * ndw;
+    int band_rows = 16, nbands = 1, n_alt = 0;
+    FcQuirk qk{};
+    if (p.mx_quirk) {
+        if (static_cast<long long>(rows) * cols >= 4000000ll)
+            while (band_rows < 128 && static_cast<long long>(nbatches) * ((rows + 2 * band_rows - 1) / (2 * band_rows)) * nframes >= 4ll * ctx->num_cus) band_rows *= 2;
+        nbands = (rows + band_rows - 1) / band_rows;
+        n_alt = nbands * nbatches * nframes;
+        // [zsum: frames x ch long long][srow: frames x rows x ch][cpart: frames x bands x cpitch] (int4 stores: 16-byte aligned)
+        const size_t n_z = static_cast<size_t>(nframes) * ch, n_srow = (static_cast<size_t>(nframes) * rows * ch + 3) & ~static_cast<size_t>(3);
+        const size_t n_cpart = static_cast<size_t>(nframes) * nbands * cpitch;
+        const size_t zbytes = (n_z * sizeof(long long) + 15) & ~static_cast<size_t>(15);
+        if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->fx_sums), &ctx->fx_sums_bytes, zbytes + (n_srow + n_cpart) * sizeof(int) + 64)) return rc;
+        long long* zsum = reinterpret_cast<long long*>(ctx->fx_sums);
+        int* srow = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->fx_sums) + zbytes);
+        HIP_TRY(ctx, hipMemsetAsync(ctx->fx_sums, 0, zbytes + n_srow * sizeof(int), ctx->stream));
+        qk.zsum = zsum;
+        qk.srow = srow;
+        qk.cpart = srow + n_srow;
+        qk.taps = p.mxt->taps_row;
+        qk.nbands = nbands;
+        qk.cpitch = cpitch;
+        qk.dr = p.mxt->dr;
+        qk.dc = p.mxt->dc;
+    }
+    {
+        TimedLaunch t(ctx, 1, nframes);
+        int* srow = const_cast<int*>(qk.srow);
+        int* cpart = const_cast<int*>(qk.cpart);
+        long long* zsum = const_cast<long long*>(qk.zsum);
+        auto kern = ch == 1 ? (G == 1 ? fc_prepass<1, 1> : (G == 2 ? fc_prepass<1, 2> : fc_prepass<1, 4>))
+                            : (G == 1 ? fc_prepass<4, 1> : (G == 2 ? fc_prepass<4, 2> : fc_prepass<4, 4>));
+        hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, p.sz.pad, pada, nbands,
+                           nbatches, cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    TimedLaunch t(ctx, 0, nframes);
+    HIP_TRY(ctx, fe->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips));
+    return BLUR_OK;
+}
+
+// the plane fallback: split a frame into f32 planes, blur each on the f32 plane path, pack with + 0.5f truncation
+__global__ void chan_split_u8_f32(const uint8_t* __restrict__ src, float* __restrict__ planes, size_t px, int ch)
+{
+    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
+        for (int c = 0; c < ch; ++c) planes[c * px + i] = static_cast<float>(src[i * ch + c]);
+}
+
+__global__ void chan_pack_f32_u8(const float* __restrict__ planes, uint8_t* __restrict__ dst, size_t px, int ch)
+{
+    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
+        for (int c = 0; c < ch; ++c)       // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
+            dst[i * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffu);
+}
+
+static int run_planes_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts)
+{
+    Prepared p;
+    if (int rc = prepare(ctx, rows, cols, sigma, opts, p, false)) return rc;
+    const size_t px = static_cast<size_t>(rows) * cols;
+    if (int rc = ensure_work(ctx, px * sizeof(float))) return rc;
+    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_planes), &ctx->ch_planes_bytes, px * ch * sizeof(float))) return rc;
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((px + 255) / 256, 4096));
+    for (int f = 0; f < nframes; ++f) {
+        const uint8_t* s = d_src + static_cast<size_t>(f) * px * ch;
+        uint8_t* d = d_dst + static_cast<size_t>(f) * px * ch;
+        hipLaunchKernelGGL(chan_split_u8_f32, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch);
+        HIP_TRY(ctx, hipGetLastError());
+        for (int c = 0; c < ch; ++c) {
+            float* plane = ctx->ch_planes + c * px;
+            if (int rc = launch_rowpass<float, 1>(ctx, plane, ctx->work, rows, cols, p.sz.pad, *p.row, p.m_row)) return rc;
+            if (int rc = launch_colpass<float, 1>(ctx, ctx->work, plane, rows, cols, p.sz.pad, *p.col, p.m_col, p.col_group)) return rc;
+        }
+        hipLaunchKernelGGL(chan_pack_f32_u8, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return BLUR_OK;
+}
+
+static int blur_u8_batch_impl(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                              const blur_opts* opts)
+{
+    // the arguments first, without the device (ctx may be NULL here: the status is the same)
+    if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
+    if (!d_src || !d_dst || nframes < 0) return fail(ctx, BLUR_ERR_INVALID, "null frame pointer or negative frame count");
+    if (rows <= 0 || cols <= 0 || !(sigma > 0)) return fail(ctx, BLUR_ERR_INVALID, "rows, cols and sigma must be positive");
+    {
+        const Sizing sz = pffft_sizing(rows, cols, sigma);
+        if (sz.pad > rows - 1 || sz.pad > cols - 1)
+            return fail(ctx, BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1: reflect-101 would read outside the image (README.md:33-38)");
+    }
+    if (!ctx) return BLUR_ERR_INVALID;
+    if (channels == 3) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
+    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
+    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, "1- and 4-channel images: engine must be AUTO, FUSED or FFT");
+    // The fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED: a kernel for the pad, the frame and quirk limits),
+    // the plane fallback elsewhere.  AUTO too: where the u8c3 policy passes the fused engine over for a compile-time FFT family (frames
+    // under 1 MP, pad > 152 on 6 MP), the alternative here is the run-time-planned plane path, three to four times slower than the
+    // fused kernel (4K sigma 50, 8 frames: 0.146 ms per 1-channel frame, 0.568 per 4-channel one, on the plane path)
+    Prepared p;
+    std::string note;
+    if (choice != BLUR_ENGINE_FFT) {
+        blur_opts fo;
+        blur_opts_default(&fo);
+        if (opts) fo = *opts;
+        fo.engine = BLUR_ENGINE_FUSED;
+        const int rc = prepare(ctx, rows, cols, sigma, &fo, p, true);
+        if (rc == BLUR_ERR_UNSUPPORTED && choice == BLUR_ENGINE_AUTO) {
+            p = Prepared{};
+            note = ctx->err;
+            ctx->err.clear();                    // (not a failure of this call)
+        } else if (rc) return rc;
+        if (p.fx && static_cast<long long>(rows) * cols * channels > 0xfffff000ll) {
+            if (choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused matrix-core engine: frame too large for 32-bit offsets");
+            p.fx = nullptr;
+            note = "fused matrix-core engine: frame too large for 32-bit offsets";
+        }
+    }
+    if (nframes == 0) return BLUR_OK;
+    const size_t fb = static_cast<size_t>(rows) * cols * channels;
+    // overlap of the source and destination ranges (over the whole batch): the fused kernel reads its neighbours' pixels while it
+    // writes, and the plane path writes frame f before it reads frame f + 1.  An in-place call of the plane path needs no copy
+    // (frame f is read whole before it is written); every other overlap reads from a copy
+    const uint8_t* lo = d_src < d_dst ? d_src : d_dst;
+    const uint8_t* hi = d_src < d_dst ? d_dst : d_src;
+    const bool overlap = static_cast<size_t>(hi - lo) < fb * nframes;
+    if (overlap && (p.fx || d_src != d_dst)) {
+        if (d_src == d_dst) {       // in place: in parts of at most 1 GiB (a part's result never touches a later part's source)
+            const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
+            if (static_cast<size_t>(nframes) > cap) {
+                for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
+                    const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
+                    uint8_t* part = d_dst + static_cast<size_t>(f0) * fb;
+                    if (int rc = blur_u8_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts)) return rc;
+                }
+                return BLUR_OK;
+            }
+        }
+        if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
+        d_src = ctx->ch_copy;
+    }
+    if (p.fx) {
+        ctx->last_family = 6;
+        return run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
+    }
+    blur_opts o;
+    blur_opts_default(&o);
+    if (opts) o = *opts;
+    o.engine = BLUR_ENGINE_FFT;
+    if (int rc = run_planes_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, &o)) return rc;
+    ctx->last_family = 0;
+    ctx->engine_note = note;
+    return BLUR_OK;
+}
+
+// ======================================================================================
 // C ABI
 // ======================================================================================
 // ---- whole-image 2D path: helpers (the entry points are below, blur_pocketfft2d_*) ----
@@ -1837,6 +2029,8 @@ int blur_ctx_destroy(blur_ctx* ctx)
     if (ctx->work) (void)hipFree(reinterpret_cast<char*>(ctx->work) - kWorkGuard);
     if (ctx->work2) (void)hipFree(ctx->work2);
     if (ctx->box_tmp) (void)hipFree(ctx->box_tmp);
+    if (ctx->ch_planes) (void)hipFree(ctx->ch_planes);
+    if (ctx->ch_copy) (void)hipFree(ctx->ch_copy);
     if (ctx->host_stage) (void)hipFree(ctx->host_stage);
     if (ctx->pipe.ready) {
         (void)hipStreamSynchronize(ctx->pipe.h2d);
@@ -2993,6 +3187,64 @@ int blur_fastboxblur_u8_batch_multi_dev(blur_multi* m, uint8_t* d_inout, int nfr
 int blur_fastboxblur_u8_batch_multi_host(blur_multi* m, uint8_t* inout, int nframes, int w, int h, int channels, int ksize, int passes)
 {
     return box_multi(m, inout, nframes, w, h, channels, ksize, passes, 0);
+}
+
+// 1-, 3- and 4-channel u8 images (channels == 3: the u8c3 entry points)
+int blur_gaussian_u8_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                               const blur_opts* opts)
+{
+    return blur_u8_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_u8_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_u8_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_u8_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
+    if (!src || !dst || rows <= 0 || cols <= 0) return fail(ctx, BLUR_ERR_INVALID, "null image or non-positive size");
+    if (!ctx) return BLUR_ERR_INVALID;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = static_cast<size_t>(rows) * cols * channels, half = (bytes + 255) & ~static_cast<size_t>(255);
+    void* dv = nullptr;
+    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;      // source and destination: no in-place copy
+    uint8_t* d = static_cast<uint8_t*>(dv);
+    int rc = BLUR_OK;
+    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) rc = blur_u8_batch_impl(ctx, d, d + half, 1, rows, cols, channels, sigma, opts);
+    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
+    return rc;
+}
+
+static int gaussian_u8_multi(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, int channels, double sigma,
+                             const blur_opts* opts, int location)
+{
+    if (!m) return BLUR_ERR_INVALID;
+    if (channels != 1 && channels != 3 && channels != 4) { m->err = "channels must be 1, 3 or 4"; return BLUR_ERR_INVALID; }
+    if (!src || !dst || nframes < 0) { m->err = "null frame pointer or negative frame count"; return BLUR_ERR_INVALID; }
+    if (nframes == 0) return BLUR_OK;
+    // frames queued by the caller on devices[0] must be complete before other devices (and other streams) read them
+    if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
+    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels : 0;
+    return blur_multi_run(m, src, dst, nframes, fb, location, [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) {
+        return blur_u8_batch_impl(c, in, out, n, rows, cols, channels, sigma, opts);
+    });
+}
+
+int blur_gaussian_u8_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                     const blur_opts* opts)
+{
+    return gaussian_u8_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, 1);
+}
+
+int blur_gaussian_u8_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, int channels, double sigma,
+                                      const blur_opts* opts)
+{
+    return gaussian_u8_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
 }
 
 int blur_convolve_lines_c32_dev(blur_ctx* ctx, const float* d_in, float* d_out, int nlines, int n, const float* multipliers)

@@ -1,0 +1,3 @@
+// fused matrix-core kernel for 1- and 4-channel images, 5 window blocks of 16 positions: pad <= 24; one channel per workgroup
+#include "fc_kernels.hpp"
+BLUR_FC(5)

@@ -122,8 +122,9 @@ int blur_ctx_synchronize(blur_ctx* ctx);
 /* message of the last failing call on this ctx ("" if none); ctx may be NULL for
    failures of blur_ctx_create */
 const char* blur_last_error(const blur_ctx* ctx);
-/* which kernels the last u8c3 blur on this ctx ran on: returns 0 run-time-planned FFT, 1 specialised rows-first FFT, 2 wave-resident
-   FFT, 3 whole-image 2D FFT, 4 two-kernel matrix-core engine, 6 fused matrix-core kernel (-1: none yet), and writes into note
+/* which kernels the last u8c3 blur (or blur_gaussian_u8_*) on this ctx ran on: returns 0 run-time-planned FFT, 1 specialised rows-first
+   FFT, 2 wave-resident FFT, 3 whole-image 2D FFT, 4 two-kernel matrix-core engine, 6 fused matrix-core kernel, 7 tiled wave-resident
+   FFT (-1: none yet); 1- and 4-channel images report 6 (their fused kernel) or 0 (the plane fallback), and it writes into note
    (n bytes, may be NULL) the engine's name and, under BLUR_ENGINE_AUTO, why a faster engine was passed over -- e.g.
    "two-kernel matrix-core engine (not taken: wide fused kernel (pad 73 .. 168): frames below 1 MP run on two kernels or the FFT kernels)" */
 int blur_last_engine(const blur_ctx* ctx, char* note, size_t n);
@@ -153,6 +154,24 @@ int blur_gaussian_u8c3_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d
 /* One float32 plane (the per-channel body Source.cpp:510-564; BASELINE config 1). */
 int blur_gaussian_f32c1_dev(blur_ctx* ctx, const float* d_src, float* d_dst,
                             int rows, int cols, double sigma, const blur_opts* opts);
+
+/* 1-, 3- or 4-channel u8 frames (grayscale, BGR, BGRA / RGBA), interleaved, rows*cols*channels bytes per frame, nframes back to
+   back, DEVICE pointers.  Every channel is blurred on its own exactly as pffft_() blurs one of its three (Source.cpp:510-564: sizing
+   and kernel from (rows, cols, sigma), reflect-101, the Nyquist-slot quirk per channel plane, + 0.5f truncation); the alpha channel
+   is blurred like the others.  channels == 3 is blur_gaussian_u8c3_batch_dev.  channels 1 and 4: opts->engine AUTO takes the
+   fused matrix-core kernel wherever it applies (pad <= 168 and the fused engine's frame limits: everywhere the u8c3 call on the
+   same frame and sigma takes it, and also where that call prefers an FFT family), the f32 plane path per channel elsewhere;
+   FUSED fails with BLUR_ERR_UNSUPPORTED where the fused kernel does not apply; FFT always takes the plane path; other engines
+   are BLUR_ERR_UNSUPPORTED.  d_dst may equal d_src; other overlaps are detected over the whole batch and read from a copy.
+   BLUR_ERR_INVALID: channels not in {1, 3, 4}, a NULL pointer, nframes < 0, rows, cols or sigma <= 0; BLUR_ERR_UNSUPPORTED: pad >
+   min(rows, cols) - 1.  These are checked before the device is touched (ctx may then be NULL); nframes == 0 is a no-op. */
+int blur_gaussian_u8_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels,
+                               double sigma, const blur_opts* opts);
+int blur_gaussian_u8_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int rows, int cols, int channels, double sigma,
+                         const blur_opts* opts);
+/* the same for one frame in HOST memory: copy in, blur, copy out, synchronise */
+int blur_gaussian_u8_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, int channels, double sigma,
+                          const blur_opts* opts);
 
 /* HOST pointers: copy in, blur, copy out, synchronise (what a cv::Mat caller needs). */
 int blur_gaussian_u8c3_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst,
@@ -278,6 +297,11 @@ int blur_gaussian_u8c3_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint
                                        double sigma, const blur_opts* opts);
 int blur_gaussian_u8c3_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols,
                                         double sigma, const blur_opts* opts);
+/* blur_gaussian_u8_batch_dev over a batch, sharded by frame exactly like the two calls above */
+int blur_gaussian_u8_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels,
+                                     double sigma, const blur_opts* opts);
+int blur_gaussian_u8_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, int channels,
+                                      double sigma, const blur_opts* opts);
 /* fastboxblur over a batch, sharded by frame exactly like the two calls above, in place (blur_fastboxblur_u8_batch_dev on
    each shard); arguments and errors as blur_fastboxblur_u8_batch_dev, nframes == 0 is a no-op, shards without frames idle. */
 int blur_fastboxblur_u8_batch_multi_dev(blur_multi* m, uint8_t* d_inout, int nframes, int w, int h, int channels,

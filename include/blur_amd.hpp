@@ -208,6 +208,19 @@ template <class Mat, class = decltype(std::declval<Mat&>().size[0])> void pffft_
     pffft_(reinterpret_cast<uint8_t*>(image.data), static_cast<int>(image.size[0]), static_cast<int>(image.size[1]), nsmooth);
 }
 
+// gaussian_blur: pffft_'s blur for 1-, 3- or 4-channel u8 images (grayscale, BGR, BGRA / RGBA), in place; every channel, alpha
+// included, is blurred on its own exactly as pffft_ blurs one of its three (blur_gaussian_u8_host).  Unlike pffft_(Mat&), which
+// assumes 3 channels as the reference does, the Mat overload reads image.channels().
+inline void gaussian_blur(uint8_t* data, int rows, int cols, int channels, double sigma, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u8_host(ctx, data, data, rows, cols, channels, sigma, opts), "gaussian_blur");
+}
+template <class Mat, class = decltype(std::declval<Mat&>().channels())> void gaussian_blur(Mat& image, double sigma)
+{
+    gaussian_blur(reinterpret_cast<uint8_t*>(image.data), static_cast<int>(image.size[0]), static_cast<int>(image.size[1]), static_cast<int>(image.channels()), sigma);
+}
+
 // pocketfft_1D(image, sigma) (Source.cpp:280-392) and pocketfft_2D(image, sigma) (Source.cpp:143-277): the two
 // pocketfft paths multiply all N/2+1 bins with the kernel's own spectrum (no Nyquist-slot quirk) and, inside the
 // cropped image, both equal the linear convolution of the reflect-101 extended image -- the engine's

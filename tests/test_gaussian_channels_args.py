@@ -1,0 +1,134 @@
+"""blur_gaussian_u8_*: argument validation that needs no device (the checks run before the context is touched, so ctx may be
+NULL), the bindings of the new entry points, and the host-side geometry of the 1- / 4-channel fused kernel's staging (fc_kernels.hpp)
+mirrored in Python."""
+import ctypes as C
+
+import pytest
+
+INVALID, UNSUPPORTED = 1, 2
+
+
+def lib():
+    from blur_algorithms_amd import _lib
+    return _lib.load()
+
+
+def opts():
+    from blur_algorithms_amd._lib import BlurOpts
+    o = BlurOpts()
+    lib().blur_opts_default(C.byref(o))
+    return o
+
+
+BUF = (C.c_uint8 * 64)()
+P = C.addressof(BUF)
+
+
+@pytest.mark.parametrize("channels", [0, 2, 5, -1, 3 * 256])
+def test_bad_channel_count(channels):
+    o = opts()
+    L = lib()
+    assert L.blur_gaussian_u8_batch_dev(None, P, P, 1, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+    assert L.blur_gaussian_u8_dev(None, P, P, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+    assert L.blur_gaussian_u8_host(None, P, P, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+    assert L.blur_gaussian_u8_batch_multi_dev(None, P, P, 1, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+    assert L.blur_gaussian_u8_batch_multi_host(None, P, P, 1, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+
+
+@pytest.mark.parametrize("channels", [1, 3, 4])
+def test_null_pointers_and_counts(channels):
+    o = opts()
+    L = lib()
+    for src, dst in ((None, P), (P, None), (None, None)):
+        assert L.blur_gaussian_u8_batch_dev(None, src, dst, 1, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+        assert L.blur_gaussian_u8_dev(None, src, dst, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+        assert L.blur_gaussian_u8_host(None, src, dst, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+    assert L.blur_gaussian_u8_batch_dev(None, P, P, -1, 4, 4, channels, 1.0, C.byref(o)) == INVALID
+    for rows, cols, sigma in ((0, 4, 1.0), (4, -1, 1.0), (4, 4, 0.0), (4, 4, -2.0)):
+        assert L.blur_gaussian_u8_batch_dev(None, P, P, 1, rows, cols, channels, sigma, C.byref(o)) == INVALID
+
+
+@pytest.mark.parametrize("channels", [1, 3, 4])
+def test_sigma_too_large_for_the_shape(channels):
+    """pad > min(rows, cols) - 1 -> BLUR_ERR_UNSUPPORTED (the reference's reflect-101 would read outside the image), before the
+    device; a valid call without a context is BLUR_ERR_INVALID"""
+    import blur_algorithms_amd as B
+    o = opts()
+    L = lib()
+    rows, cols = 40, 90
+    big = 30.0
+    assert B.pffft_sizing(rows, cols, big)["pad"] > rows - 1
+    assert L.blur_gaussian_u8_batch_dev(None, P, P, 1, rows, cols, channels, big, C.byref(o)) == UNSUPPORTED
+    assert L.blur_gaussian_u8_dev(None, P, P, rows, cols, channels, big, C.byref(o)) == UNSUPPORTED
+    small = 2.0
+    assert B.pffft_sizing(rows, cols, small)["pad"] <= rows - 1
+    assert L.blur_gaussian_u8_batch_dev(None, P, P, 1, rows, cols, channels, small, C.byref(o)) == INVALID
+
+
+def test_python_shapes():
+    from blur_algorithms_amd.api import _gauss_frames_shape
+    assert _gauss_frames_shape((5, 7)) == (1, 5, 7, 1)
+    assert _gauss_frames_shape((5, 7, 4)) == (1, 5, 7, 4)
+    assert _gauss_frames_shape((3, 5, 7, 1)) == (3, 5, 7, 1)
+    for bad in ((5, 7, 2), (5,), (2, 5, 7, 5), (1, 2, 3, 4, 5)):
+        with pytest.raises(ValueError):
+            _gauss_frames_shape(bad)
+
+
+# ---- host mirror of the staging geometry of fc_blur_u8 ----------------------------------------------------------------
+def fw_cfg(nkb):
+    pada = 8 * (nkb - 2)
+    win = 128 + 2 * pada
+    gpr = win // 4
+    per = (gpr + 7) // 8
+    cs = max(nkb, 9)
+    ips = (per + cs - 6) // (cs - 5)
+    return pada, win, gpr, per, cs, ips
+
+
+@pytest.mark.parametrize("nkb", [3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23])
+@pytest.mark.parametrize("ch", [1, 4])
+def test_staging_covers_the_window_once(nkb, ch):
+    """thread (row, g0) loads the groups g0 + 8 k (4 pixels = 4 ch bytes each) at byte 4 ch g0 + 32 ch k of a window row; the
+    groups past the window's last one reload group g0 (their halfs land in the row's padding); the column-pass slots 5 .. cs - 1
+    commit ips items each, which must cover all per of them"""
+    pada, win, gpr, per, cs, ips = fw_cfg(nkb)
+    assert ips * (cs - 5) >= per
+    seen = {}
+    for g0 in range(8):
+        for k in range(per):
+            inside = gpr % 8 == 0 or k < per - 1 or g0 < gpr % 8
+            off = 4 * ch * g0 + (32 * ch * k if inside else 0)
+            assert off + 4 * ch <= ch * win, "a load past the window row"
+            if inside:
+                grp = g0 + 8 * k
+                assert off == 4 * ch * grp
+                seen[grp] = seen.get(grp, 0) + 1
+    assert sorted(seen) == list(range(gpr)) and set(seen.values()) == {1}
+    # the LDS row (32 per halfs) holds every committed group: 4 g0 + 32 k + 4 <= 32 per <= pitch
+    assert 4 * 7 + 32 * (per - 1) + 4 <= 32 * per
+
+
+@pytest.mark.parametrize("ch", [1, 4])
+def test_output_stores_stay_in_the_frame(ch):
+    """CH = 1: lane q of quad Q stores pixels 4 Q .. 4 Q + 3 of row 8 gq + 4 h + q as one dword when all four lie in the image,
+    else (ragged widths) bytes for the ones that do; CH = 4: byte c of the lane's pixel.  Every pixel of a tile is stored once."""
+    for cols in (1, 2, 3, 4, 5, 127, 128, 129, 130, 131, 517):
+        for x0 in range(0, cols, 128):
+            written = {}
+            for wave in range(4):
+                for m in range(32):
+                    if ch == 1:
+                        xq = x0 + 32 * wave + 4 * (m >> 2)
+                        qn = 0 if xq >= cols else min(4, cols - xq)
+                        px = list(range(xq, xq + 4)) if qn == 4 else list(range(xq, xq + qn))
+                    else:
+                        xcol = x0 + 32 * wave + m
+                        px = [xcol] if xcol < cols else []
+                    for x in px:
+                        assert x < cols
+                        written[x] = written.get(x, 0) + 1
+            want = set(range(x0, min(x0 + 128, cols)))
+            assert set(written) == want
+            # CH = 1: the four lanes of a quad store the same pixels, each in its own row; CH = 4: one lane per pixel
+            assert set(written.values()) == {4 if ch == 1 else 1}
