@@ -118,6 +118,21 @@ def _gauss_frames_shape(shape):
     return n, rows, cols, ch
 
 
+def _gauss_f32_frames_shape(shape):
+    """float32 [rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4} -> (n, rows, cols, C)"""
+    if len(shape) == 2:
+        n, rows, cols, ch = 1, shape[0], shape[1], 1
+    elif len(shape) == 3:
+        n, (rows, cols, ch) = 1, shape
+    elif len(shape) == 4:
+        n, rows, cols, ch = shape
+    else:
+        n = rows = cols = ch = 0
+    if ch not in (1, 3, 4) or rows <= 0 or cols <= 0:
+        raise ValueError("expected float32 [rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4}")
+    return n, rows, cols, ch
+
+
 def fft_plan_radices(n):
     r = (C.c_int * 16)()
     k = _L().blur_fft_plan_radices(int(n), r)
@@ -480,6 +495,40 @@ class BlurContext:
         self._check(self._lib.blur_gaussian_u8_batch_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
         return dst
 
+    def gaussian_f32(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
+        """Gaussian blur of a float32 image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows, cols, C].  Every
+        channel is blurred on its own as pffft_ blurs one of its planes, without the + 0.5f truncation (blur_gaussian_f32_batch_dev).
+        engine: None (the library's choice), "fused" or "fft".
+
+        torch CUDA tensor: asynchronous on torch's current stream, returns `out` (default: in place).  numpy array: host round trip,
+        returns a new array.
+        """
+        o = self._opts(nyquist_quirk, engine=engine)
+        if isinstance(image, np.ndarray):
+            if image.dtype != np.float32:
+                raise ValueError("expected a float32 array")
+            a = np.ascontiguousarray(image)
+            n, rows, cols, ch = _gauss_f32_frames_shape(a.shape)
+            res = np.empty_like(a) if out is None else out
+            if res.shape != a.shape or res.dtype != np.float32 or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must match the input")
+            fb = rows * cols * ch * 4
+            for f in range(n):
+                self._check(self._lib.blur_gaussian_f32_host(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch,
+                                                             float(sigma), C.byref(o)))
+            return res
+        import torch
+        t = image
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("expected a contiguous CUDA float32 tensor [rows, cols], [rows, cols, C] or [n, rows, cols, C]")
+        n, rows, cols, ch = _gauss_f32_frames_shape(tuple(t.shape))
+        dst = t if out is None else out
+        if dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
+            raise ValueError("out must match the input")
+        self.use_torch_stream()
+        self._check(self._lib.blur_gaussian_f32_batch_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
+        return dst
+
     def fastboxblur(self, image, ksize, passes):
         """fastboxblur(in, w, h, channels, ksize, passes), in place -- call site Source.cpp:587"""
         if isinstance(image, np.ndarray):
@@ -589,6 +638,37 @@ class BlurMulti:
         dst = t if out is None else out
         torch.cuda.synchronize(t.device)
         self._check(self._lib.blur_gaussian_u8_batch_multi_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
+        return dst
+
+    def gaussian_f32(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
+        """BlurContext.gaussian_f32 over a batch sharded by frame: frames float32 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
+        tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
+        o = BlurOpts()
+        self._lib.blur_opts_default(C.byref(o))
+        o.nyquist_quirk = 1 if nyquist_quirk else 0
+        if engine is not None:
+            o.engine = ENGINES[engine]
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.float32 or frames.ndim != 4:
+                raise ValueError("expected float32 frames [n, rows, cols, C]")
+            a = np.ascontiguousarray(frames)
+            n, rows, cols, ch = _gauss_f32_frames_shape(a.shape)
+            res = np.empty_like(a) if out is None else out
+            if res.shape != a.shape or res.dtype != np.float32 or not res.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must match the input")
+            self._check(self._lib.blur_gaussian_f32_batch_multi_host(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, float(sigma), C.byref(o)))
+            return res
+        import torch
+        t = frames
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 4
+                or t.device.index != self.devices[0]):
+            raise ValueError("expected a contiguous CUDA float32 tensor [n, rows, cols, C] on devices[0]")
+        n, rows, cols, ch = _gauss_f32_frames_shape(tuple(t.shape))
+        dst = t if out is None else out
+        if dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
+            raise ValueError("out must match the input")
+        torch.cuda.synchronize(t.device)
+        self._check(self._lib.blur_gaussian_f32_batch_multi_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
         return dst
 
     def fastboxblur(self, frames, ksize, passes):

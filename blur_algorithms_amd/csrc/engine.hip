@@ -767,6 +767,10 @@ struct blur_ctx {
     size_t ch_planes_bytes = 0;
     uint8_t* ch_copy = nullptr;      // 1- / 4-channel images: a copy of overlapping source frames
     size_t ch_copy_bytes = 0;
+    void* ff_sums = nullptr;         // float32 images, fused kernel: max|x| per frame and the quirk's sums (run_ff_f32)
+    size_t ff_sums_bytes = 0;
+    float* ff_strips = nullptr;      // float32 images, fused kernel: the edge chunks' windows
+    size_t ff_strips_bytes = 0;
     size_t box_bytes = 0;
     std::string engine_note;      // BLUR_ENGINE_AUTO: why the last call's choice passed over a faster engine ("" if it did not)
     int last_family = -1;         // kernels the last u8c3 blur used: 0 run-time plans, 1 specialised rows-first, 2 wave-resident, 3 whole-image 2D, 4 matrix-core (two kernels), 6 fused matrix-core
@@ -1882,6 +1886,189 @@ static int blur_u8_batch_impl(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_ds
 }
 
 // ======================================================================================
+// float32 images of 1, 3 or 4 channels (blur_gaussian_f32_*): every channel blurred on its own as pffft_() blurs one of its planes,
+// without the + 0.5f truncation
+// ======================================================================================
+#include "ff_registry.hpp"
+
+// the fused kernel (ff_kernels.hpp): the pre-pass (max|x|, the quirk's sums, the edge chunks' strips), the quirk's finalisation,
+// then the kernel.  Frames are disjoint from the destination here (blur_f32_batch_impl copies overlapping ones first).  Every
+// partition of a sum (bands, batches) depends on the frame's shape only: a frame gives the same bits alone and in a batch.
+static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
+{
+    const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
+    const FfEntry* fe = find_ff_entry(nkb);
+    if (!fe || !ff_class_ok(nkb, ch)) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for float32 images: no kernel instantiated for this pad and channel count");
+    FxGeom g{ rows, cols, p.sz.pad, nframes, 0, (rows + 31) / 32, fx_right_strips(cols, pada), ctx->num_xcds };
+    const int chunks_x = (cols + kFxChunk - 1) / kFxChunk, win = kFxChunk + 2 * pada, nstrips = fx_left_strips(pada) + g.nright;
+    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ff_strips), &ctx->ff_strips_bytes,
+                            (static_cast<size_t>(nframes) * nstrips * rows * win * ch + 16) * sizeof(float))) return rc;
+    const int strip_blocks = static_cast<int>((static_cast<long long>(rows) * ch * win + 255) / 256);
+    const int n_strip = strip_blocks * nstrips * nframes;
+    const int G = ff_groups_per_thread(cols, ch), ne = cols * ch, nbatches = (ne + ff_batch_stride(ch) * G - 1) / (ff_batch_stride(ch) * G);
+    // bands of rows: enough workgroups per frame to read it at the memory's rate (from the frame's shape alone)
+    int band_rows = 16;
+    while (band_rows < 128 && static_cast<long long>(nbatches) * ((rows + 2 * band_rows - 1) / (2 * band_rows)) >= 512) band_rows *= 2;
+    const int nbands = (rows + band_rows - 1) / band_rows, n_alt = nbands * nbatches * nframes;
+    const bool quirk = p.mx_quirk;
+    // [mbits: frames][zsum: frames x ch][srow: frames x rows x ch][spart: frames x batches x rows x ch][cpart: frames x bands x ne]
+    const size_t n_m = (static_cast<size_t>(nframes) + 1) / 2, n_z = static_cast<size_t>(nframes) * ch, n_srow = static_cast<size_t>(nframes) * rows * ch;
+    const size_t n_spart = quirk ? n_srow * nbatches : 0, n_cpart = quirk ? static_cast<size_t>(nframes) * nbands * ne : 0;
+    if (int rc = ensure_buf(ctx, &ctx->ff_sums, &ctx->ff_sums_bytes, (n_m + n_z + (quirk ? n_srow : 0) + n_spart + n_cpart) * sizeof(double) + 64)) return rc;
+    double* base = static_cast<double*>(ctx->ff_sums);
+    unsigned* mbits = reinterpret_cast<unsigned*>(base);
+    double* zsum = base + n_m;
+    double* srow = zsum + n_z;
+    double* spart = srow + (quirk ? n_srow : 0);
+    double* cpart = spart + n_spart;
+    HIP_TRY(ctx, hipMemsetAsync(mbits, 0, static_cast<size_t>(nframes) * sizeof(unsigned), ctx->stream));
+    FfQuirk qk{};
+    qk.mbits = mbits;
+    qk.bscale = 1.0;
+    if (quirk) {
+        qk.srow = srow;
+        qk.cpart = cpart;
+        qk.zsum = zsum;
+        qk.taps = p.mxt->taps_row;
+        qk.nbands = nbands;
+        qk.cpitch = ne;
+        qk.dr = p.mxt->dr;
+        qk.dc = p.mxt->dc;
+        qk.bscale = 1.0 + std::fabs(static_cast<double>(p.mxt->dr)) * (static_cast<double>(cols) + 2.0 * p.sz.pad);     // |Srow| <= (cols + 2 pad) max|x|
+    }
+    {
+        TimedLaunch t(ctx, 1, nframes);
+        auto pick = [&](auto k1, auto k2, auto k4) { return G == 1 ? k1 : (G == 2 ? k2 : k4); };
+        auto kern = ch == 1 ? pick(ff_prepass<1, 1>, ff_prepass<1, 2>, ff_prepass<1, 4>)
+                            : (ch == 3 ? pick(ff_prepass<3, 1>, ff_prepass<3, 2>, ff_prepass<3, 4>) : pick(ff_prepass<4, 1>, ff_prepass<4, 2>, ff_prepass<4, 4>));
+        hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, mbits, spart, cpart, ctx->ff_strips, rows, cols, p.sz.pad, pada, nbands,
+                           nbatches, ne, n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0);
+        HIP_TRY(ctx, hipGetLastError());
+        if (quirk) {
+            auto fin = ch == 1 ? ff_finalize<1> : (ch == 3 ? ff_finalize<3> : ff_finalize<4>);
+            hipLaunchKernelGGL(fin, dim3(nframes), dim3(256), 0, ctx->stream, spart, srow, zsum, rows, p.sz.pad, nbatches);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    TimedLaunch t(ctx, 0, nframes);
+    HIP_TRY(ctx, fe->blur_f32(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, ctx->ff_strips));
+    return BLUR_OK;
+}
+
+// the plane fallback: split a frame into f32 planes, blur each on the f32 plane path, interleave the results
+__global__ void chan_split_f32(const float* __restrict__ src, float* __restrict__ planes, size_t px, int ch)
+{
+    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
+        for (int c = 0; c < ch; ++c) planes[c * px + i] = src[i * ch + c];
+}
+
+__global__ void chan_pack_f32(const float* __restrict__ planes, float* __restrict__ dst, size_t px, int ch)
+{
+    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
+        for (int c = 0; c < ch; ++c) dst[i * ch + c] = planes[c * px + i];
+}
+
+static int run_planes_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts)
+{
+    Prepared p;
+    if (int rc = prepare(ctx, rows, cols, sigma, opts, p, false)) return rc;
+    const size_t px = static_cast<size_t>(rows) * cols;
+    if (int rc = ensure_work(ctx, px * sizeof(float))) return rc;
+    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_planes), &ctx->ch_planes_bytes, px * ch * sizeof(float))) return rc;
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((px + 255) / 256, 4096));
+    for (int f = 0; f < nframes; ++f) {
+        const float* s = d_src + static_cast<size_t>(f) * px * ch;
+        float* d = d_dst + static_cast<size_t>(f) * px * ch;
+        hipLaunchKernelGGL(chan_split_f32, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch);
+        HIP_TRY(ctx, hipGetLastError());
+        for (int c = 0; c < ch; ++c) {
+            float* plane = ctx->ch_planes + c * px;
+            if (int rc = launch_rowpass<float, 1>(ctx, plane, ctx->work, rows, cols, p.sz.pad, *p.row, p.m_row)) return rc;
+            if (int rc = launch_colpass<float, 1>(ctx, ctx->work, plane, rows, cols, p.sz.pad, *p.col, p.m_col, p.col_group)) return rc;
+        }
+        hipLaunchKernelGGL(chan_pack_f32, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return BLUR_OK;
+}
+
+static int blur_f32_batch_impl(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                               const blur_opts* opts)
+{
+    // the arguments first, without the device (ctx may be NULL here: the status is the same)
+    if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
+    if (!d_src || !d_dst || nframes < 0) return fail(ctx, BLUR_ERR_INVALID, "null frame pointer or negative frame count");
+    if (rows <= 0 || cols <= 0 || !(sigma > 0)) return fail(ctx, BLUR_ERR_INVALID, "rows, cols and sigma must be positive");
+    {
+        const Sizing sz = pffft_sizing(rows, cols, sigma);
+        if (sz.pad > rows - 1 || sz.pad > cols - 1)
+            return fail(ctx, BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1: reflect-101 would read outside the image (README.md:33-38)");
+    }
+    if (!ctx) return BLUR_ERR_INVALID;
+    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
+    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, "float32 images: engine must be AUTO, FUSED or FFT");
+    // the fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED, a class instantiated for the channel count, the
+    // frame's bytes within 32-bit offsets), the plane fallback elsewhere
+    Prepared p;
+    std::string note;
+    if (choice != BLUR_ENGINE_FFT) {
+        blur_opts fo;
+        blur_opts_default(&fo);
+        if (opts) fo = *opts;
+        fo.engine = BLUR_ENGINE_FUSED;
+        const int rc = prepare(ctx, rows, cols, sigma, &fo, p, true);
+        if (rc == BLUR_ERR_UNSUPPORTED && choice == BLUR_ENGINE_AUTO) {
+            p = Prepared{};
+            note = ctx->err;
+            ctx->err.clear();                    // (not a failure of this call)
+        } else if (rc) return rc;
+        const char* why = nullptr;
+        if (p.fx && !ff_class_ok(p.fx->nkb, channels)) why = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
+        else if (p.fx && static_cast<long long>(rows) * cols * channels * 4 > 0xfffff000ll) why = "fused matrix-core engine: frame too large for 32-bit offsets";
+        if (why) {
+            if (choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, why);
+            p.fx = nullptr;
+            note = why;
+        }
+    }
+    if (nframes == 0) return BLUR_OK;
+    const size_t fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(float);
+    // overlap over the whole batch: as blur_u8_batch_impl
+    const char* lo = reinterpret_cast<const char*>(d_src < d_dst ? d_src : d_dst);
+    const char* hi = reinterpret_cast<const char*>(d_src < d_dst ? d_dst : d_src);
+    const bool overlap = static_cast<size_t>(hi - lo) < fb * nframes;
+    if (overlap && (p.fx || d_src != d_dst)) {
+        if (d_src == d_dst) {       // in place: in parts of at most 1 GiB (a part's result never touches a later part's source)
+            const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
+            if (static_cast<size_t>(nframes) > cap) {
+                for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
+                    const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
+                    float* part = d_dst + static_cast<size_t>(f0) * fe;
+                    if (int rc = blur_f32_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts)) return rc;
+                }
+                return BLUR_OK;
+            }
+        }
+        if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
+        d_src = reinterpret_cast<const float*>(ctx->ch_copy);
+    }
+    if (p.fx) {
+        ctx->last_family = 6;
+        return run_ff_f32(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
+    }
+    blur_opts o;
+    blur_opts_default(&o);
+    if (opts) o = *opts;
+    o.engine = BLUR_ENGINE_FFT;
+    if (int rc = run_planes_f32(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, &o)) return rc;
+    ctx->last_family = 0;
+    ctx->engine_note = note;
+    return BLUR_OK;
+}
+
+// ======================================================================================
 // C ABI
 // ======================================================================================
 // ---- whole-image 2D path: helpers (the entry points are below, blur_pocketfft2d_*) ----
@@ -2031,6 +2218,8 @@ int blur_ctx_destroy(blur_ctx* ctx)
     if (ctx->box_tmp) (void)hipFree(ctx->box_tmp);
     if (ctx->ch_planes) (void)hipFree(ctx->ch_planes);
     if (ctx->ch_copy) (void)hipFree(ctx->ch_copy);
+    if (ctx->ff_sums) (void)hipFree(ctx->ff_sums);
+    if (ctx->ff_strips) (void)hipFree(ctx->ff_strips);
     if (ctx->host_stage) (void)hipFree(ctx->host_stage);
     if (ctx->pipe.ready) {
         (void)hipStreamSynchronize(ctx->pipe.h2d);
@@ -3245,6 +3434,69 @@ int blur_gaussian_u8_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t
                                       const blur_opts* opts)
 {
     return gaussian_u8_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
+}
+
+// float32 images of 1, 3 or 4 channels
+int blur_gaussian_f32_batch_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                const blur_opts* opts)
+{
+    return blur_f32_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_f32_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_f32_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_f32_host(blur_ctx* ctx, const float* src, float* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
+    if (!src || !dst || rows <= 0 || cols <= 0 || !(sigma > 0)) return fail(ctx, BLUR_ERR_INVALID, "null image or non-positive size");
+    {
+        const Sizing sz = pffft_sizing(rows, cols, sigma);
+        if (sz.pad > rows - 1 || sz.pad > cols - 1)
+            return fail(ctx, BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1: reflect-101 would read outside the image (README.md:33-38)");
+    }
+    if (!ctx) return BLUR_ERR_INVALID;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = static_cast<size_t>(rows) * cols * channels * sizeof(float), half = (bytes + 255) & ~static_cast<size_t>(255);
+    void* dv = nullptr;
+    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;      // source and destination: no in-place copy
+    char* d = static_cast<char*>(dv);
+    int rc = BLUR_OK;
+    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) rc = blur_f32_batch_impl(ctx, reinterpret_cast<const float*>(d), reinterpret_cast<float*>(d + half), 1, rows, cols, channels, sigma, opts);
+    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
+    return rc;
+}
+
+static int gaussian_f32_multi(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels, double sigma,
+                              const blur_opts* opts, int location)
+{
+    if (!m) return BLUR_ERR_INVALID;
+    if (channels != 1 && channels != 3 && channels != 4) { m->err = "channels must be 1, 3 or 4"; return BLUR_ERR_INVALID; }
+    if (!src || !dst || nframes < 0) { m->err = "null frame pointer or negative frame count"; return BLUR_ERR_INVALID; }
+    if (nframes == 0) return BLUR_OK;
+    if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
+    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels * sizeof(float) : 0;
+    return blur_multi_run(m, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nframes, fb, location,
+                          [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) {
+                              return blur_f32_batch_impl(c, reinterpret_cast<const float*>(in), reinterpret_cast<float*>(out), n, rows, cols, channels, sigma, opts);
+                          });
+}
+
+int blur_gaussian_f32_batch_multi_dev(blur_multi* m, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                      const blur_opts* opts)
+{
+    return gaussian_f32_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, 1);
+}
+
+int blur_gaussian_f32_batch_multi_host(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels, double sigma,
+                                       const blur_opts* opts)
+{
+    return gaussian_f32_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
 }
 
 int blur_convolve_lines_c32_dev(blur_ctx* ctx, const float* d_in, float* d_out, int nlines, int n, const float* multipliers)

@@ -1,0 +1,625 @@
+// ff_kernels.hpp -- the fused matrix-core kernel for float32 images of 1, 3 or 4 channels, every window class (NKB = 3 .. 23
+// blocks of 16 positions: pad <= 168).
+//
+// The structure is fc_kernels.hpp's: a workgroup handles ONE channel of a strip of 128 pixel columns (channel fastest in the task
+// list), stages its window through LDS, runs the row pass, the hand-off inside the registers, the sliding column-pass accumulators
+// and the emission.  What a float input changes:
+//   * range: each frame gets a power-of-two scale s = 2^e (ff_scale_exp) with max|x| s B <= 2^14, B = 1 + |dr| (cols + 2 pad) the
+//     bound of the row pass's quirk term relative to max|x| (none without the quirk).  Every V of the hand-off is then below 2^14,
+//     inside binary16's normal range with 4x headroom.  max|x| comes from the pre-pass on the device (an integer atomicMax on the
+//     bits of |x|: the same result in any order); nothing waits for the host;
+//   * staging: x s is split into hi = f16(x s) and lo = f16(x s - hi); the window in LDS is two binary16 planes (hi, lo);
+//   * row pass: x_hi t_hi + x_hi t_lo + x_lo t_hi per window block, three products where the u8 kernels take two (x_lo t_lo is
+//     dropped, as the column pass drops V_lo t_lo).  The taps keep their 2^14 scaling: every product of two binary16 values is exact
+//     in the f32 accumulator, and V = acc 2^-14;
+//   * emission: out = tfin 2^-14 / s + the column term (unscaled), stored as f32: no + 0.5f, no clamping;
+//   * loads: CH = 1 one dwordx4 per group of 4 pixels; CH = 3 / 4 the channel's four floats of the group (strided dwords; the
+//     channel tasks of a strip meet in L2);  stores: one dword per lane and output row (32 lanes: 128 contiguous bytes for CH = 1);
+//   * the quirk's sums are floating point: f32 products summed in double, every reduction in a fixed order (no float atomics), so
+//     a frame gives the same bits alone and inside a batch.
+// The accumulator budget is fw_kernels.hpp's: (NKB - 1) / 2 <= 11 tiles of one channel.
+#pragma once
+#include "fw_kernels.hpp"
+
+namespace blur_amd {
+
+// The scale exponent of a frame: e with M B 2^e in [2^13, 2^14) (M = max|x| > 0), clamped to [-125, 125] so that 2^e and 2^-e are
+// normal floats; M = 0 (and NaN) take e = 0.
+__host__ __device__ inline int ff_scale_exp(float maxabs, double bscale)
+{
+    if (!(maxabs > 0.f)) return 0;
+    int k = 0;
+    (void)frexp(static_cast<double>(maxabs) * bscale, &k);          // M B = m 2^k, m in [0.5, 1)
+    const int e = 14 - k;
+    return e < -125 ? -125 : (e > 125 ? 125 : e);
+}
+
+// What the fused float kernel reads besides the image:
+//   mbits[frame]                        bits of max|x| over the frame (the pre-pass)
+//   srow [frame][row][CH]               Srow(r, c) = sum_x wx(x) img[r][x][c]                  (ff_finalize)
+//   cpart[frame][band][cpitch]          sum over the band's rows of wy(r) img[r][x][c] at CH x + c
+//   zsum [frame][CH]                    Z(c) = sum_r wy(r) Srow(r, c)                          (ff_finalize)
+struct FfQuirk {
+    const unsigned* mbits;
+    const double* srow;
+    const double* cpart;
+    const double* zsum;
+    const float* taps;          // the 2 pad + 1 taps of the row pass, centre at pad
+    int nbands, cpitch;
+    float dr, dc;
+    double bscale;              // B of ff_scale_exp
+};
+
+constexpr float kFfRowUnscale = 1.f / 16384.f;      // V = acc 2^-14 (the taps' scaling)
+
+template <int NKB> struct FfCfg {
+    using W = FwCfg<NKB>;
+    static constexpr int PADA = W::PADA, WIN = W::WIN, GPR = W::GPR, PER = W::PER, PW = W::PW, NT = W::NT;
+    static constexpr int BUF = W::BUF;                                // one binary16 plane of one window
+    // window buffer b, plane p (0 hi, 1 lo) at (2 b + p) BUF
+    static constexpr int TLOFF = 4 * BUF;
+    static constexpr int QOFF = TLOFF + NKB * 64 * 16;
+    static constexpr int LDS = QOFF + 2 * 2 * 32 * 4;
+    static_assert(LDS <= 160 * 1024, "the LDS of one CU");
+};
+
+// qc[xl] (xl = 0 .. 127) = the column term of pixel x0 + xl in channel c0 (unscaled), 0 right of the image.  256 threads; `scratch`
+// = LDS for (128 + 2 pad) + 2 pad + 1 doubles; ends with a barrier.
+template <int CH>
+__device__ __forceinline__ void ff_quirk_cols_tile(unsigned char* scratch, float* qc, const FfQuirk& q, int f, int x0, int c0, int cols, int pad, int tid)
+{
+    const int win = kFxChunk + 2 * pad, ntap = 2 * pad + 1;
+    double* cc = reinterpret_cast<double*>(scratch);
+    double* tp = cc + win;
+    const double* base = q.cpart + static_cast<size_t>(f) * q.nbands * q.cpitch + c0;
+    for (int p = tid; p < win; p += 256) {
+        const double* cp = base + CH * mx_refl(x0 - pad + p, cols);
+        double sum = 0.0;
+        for (int b = 0; b < q.nbands; ++b) sum += cp[static_cast<size_t>(b) * q.cpitch];
+        cc[p] = sum;
+    }
+    for (int i = tid; i < ntap; i += 256) tp[i] = static_cast<double>(q.taps[i]);
+    __syncthreads();
+    const double sp = (pad & 1) ? -1.0 : 1.0, z = q.zsum[static_cast<size_t>(f) * CH + c0];
+    if (tid < kFxChunk) {
+        const int x = x0 + tid;
+        float out = 0.f;
+        if (x < cols) {
+            const double* ccx = cc + tid;
+            double acc[4] = { 0, 0, 0, 0 };
+            int t = 0;
+            for (; t + 8 <= ntap; t += 8) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j & 3] = __builtin_fma(tp[t + j], ccx[t + j], acc[j & 3]);
+            }
+            for (; t < ntap; ++t) acc[t & 3] = __builtin_fma(tp[t], ccx[t], acc[t & 3]);
+            const double sx = ((x + pad) & 1) ? -1.0 : 1.0;
+            out = static_cast<float>(static_cast<double>(q.dc) * sp * (((acc[0] + acc[1]) + (acc[2] + acc[3])) + static_cast<double>(q.dr) * sx * z));
+        }
+        qc[tid] = out;
+    }
+    __syncthreads();
+}
+
+// One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
+template <int NKB, bool QUIRK, int CH>
+__global__ __launch_bounds__(256, 1) void ff_blur_f32(const float* __restrict__ src, float* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
+                                                      int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const float* __restrict__ strips)
+{
+    static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
+    using C = FfCfg<NKB>;
+    constexpr int PADA = C::PADA, PW = C::PW, NT = C::NT, PER = C::PER;
+    constexpr int RS = NKB;                                        // row-pass slots
+    constexpr int CS = NKB > 9 ? NKB : 9;                         // column-pass slots: hand-off 0 .. 7, emission 1 .. 4, staging from 5
+    constexpr int IPS = (PER + CS - 6) / (CS - 5);                // staging items per column-pass slot from slot 5 on
+    extern __shared__ __attribute__((aligned(16))) unsigned char ff_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = lane & 31, h = lane >> 5;
+
+    const int nx = g.nxcd, xcd = blockIdx.x % nx, in_xcd = blockIdx.x / nx, per_xcd = (ntasks + nx - 1) / nx, task = xcd * per_xcd + in_xcd;
+    if (in_xcd >= per_xcd || task >= ntasks) return;
+    const int c = task % CH, xc = (task / CH) % chunks, seg = (task / (CH * chunks)) % nseg, f = task / (CH * chunks * nseg);
+    const int x0 = xc * kFxChunk;
+    const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
+    const float* img = src + static_cast<size_t>(f) * g.rows * g.cols * CH;
+    float* out = dst + static_cast<size_t>(f) * g.rows * g.cols * CH;
+
+    // the frame's scale (ff_scale_exp): s = 2^e on the staged values, 2^-e on the results
+    const int sexp = ff_scale_exp(__uint_as_float(qk.mbits[f]), qk.bscale);
+    const float scale = ldexpf(1.f, sexp), unscale = ldexpf(1.f, -sexp);
+
+    constexpr int TLR = FW_TL_REGS < NKB ? FW_TL_REGS : NKB;
+    mx_half8 th[NKB], tlr[TLR > 0 ? TLR : 1];
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) th[kb] = frags[kb * 64 + lane];
+#pragma unroll
+    for (int kb = 0; kb < TLR; ++kb) tlr[kb] = frags[(NKB + kb) * 64 + lane];
+    {
+        mx_half8* tls = reinterpret_cast<mx_half8*>(ff_lds + C::TLOFF);
+        for (int i = tid; i < NKB * 64; i += 256) tls[i] = frags[NKB * 64 + i];
+    }
+    const mx_half8* tlp = reinterpret_cast<const mx_half8*>(ff_lds + C::TLOFF) + lane;
+    auto tlo = [&](int kb) __attribute__((always_inline)) { return kb < TLR ? tlr[kb < TLR ? kb : 0] : tlp[kb * 64]; };
+
+    float cpos = 0.f, cneg = 0.f;
+    if (QUIRK) {
+        static_assert(C::BUF >= 8 * (C::WIN + 2 * C::PADA + 1) && C::BUF >= 4 * kFxChunk, "ff_quirk_cols_tile's scratch and result fit the window buffers");
+        float* qc = reinterpret_cast<float*>(ff_lds + C::BUF);
+        ff_quirk_cols_tile<CH>(ff_lds, qc, qk, f, x0, c, g.cols, g.pad, tid);
+        const float v = qc[32 * wave + m];
+        cpos = v;
+        cneg = -v;
+        __syncthreads();
+    }
+    const int qrows = 32 * (g.ntiles + NT);
+    const double qrs = QUIRK ? static_cast<double>(qk.dr) * ((g.pad & 1) ? -1.0 : 1.0) * static_cast<double>(scale) : 0.0;
+
+    const mx_float16 zero = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    mx_float16 acc[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) acc[k] = zero;
+    mx_float16 arow = zero, tfin = zero;
+    uint32_t hl[2][2][8];
+
+    const int s0 = tile0, s1 = tile1 + NT;
+    constexpr int NLEFT = fx_left_strips(PADA);
+    const int sidx = xc < NLEFT ? xc : (xc >= chunks - g.nright ? NLEFT + xc - (chunks - g.nright) : -1);      // uniform
+    // byte offsets: a frame's bytes fit 32 bits (the engine's frame limit)
+    const uint32_t pitch = sidx >= 0 ? static_cast<uint32_t>(4 * CH * C::WIN) : 4u * CH * static_cast<uint32_t>(g.cols);
+    const float* wbase = sidx >= 0 ? strips + (static_cast<size_t>(f) * (NLEFT + g.nright) + sidx) * g.rows * (CH * C::WIN) : img + CH * (x0 - PADA);
+    const uint32_t wbytes = sidx >= 0 ? static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(4 * CH * C::WIN)
+                                      : (static_cast<uint32_t>(g.rows) * g.cols - static_cast<uint32_t>(x0 - PADA)) * static_cast<uint32_t>(4 * CH);
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), 0, wbytes, kMxRsrcWord3);
+    const int srow = 8 * (tid >> 6) + ((tid >> 4) & 3) + 4 * ((tid >> 3) & 1), g0 = tid & 7;      // (fx_kernels.hpp: the staging map)
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    uint32_t raw[PER][4];
+    double qv = 0.0;
+    // the window of step s: thread t moves channel c of the groups of 4 pixels g0 + 8 k of row srow, all requested at once
+    auto issue_window = [&](int s) __attribute__((always_inline)) {
+        const int r = mx_refl(32 * s - PADA + srow, g.rows);
+        const uint32_t off = static_cast<uint32_t>(r) * pitch + static_cast<uint32_t>(16 * CH * g0 + 4 * c);
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const bool in = (C::GPR % 8 == 0) || k < PER - 1 || g0 < C::GPR % 8;
+            const uint32_t o = in ? off + static_cast<uint32_t>(128 * CH * k) : off;
+            if (CH == 1) {
+                const u4 t = __builtin_amdgcn_raw_buffer_load_b128(rimg, o, 0, 0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) raw[k][j] = t[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) raw[k][j] = __builtin_amdgcn_raw_buffer_load_b32(rimg, o + static_cast<uint32_t>(4 * CH * j), 0, 0);
+            }
+        }
+        if (QUIRK)              // the row term of row re of V (= image row refl(re - PADA)); every thread (row tid & 31: eight copies of each value)
+            qv = qk.srow[(static_cast<size_t>(f) * g.rows + mx_refl(min(32 * s + (tid & 31), qrows - 1) - PADA, g.rows)) * CH + c];
+    };
+    // group k: x s -> hi + lo binary16 -> the two planes in LDS (one ds_write_b64 each)
+    auto commit_item = [&](int buf, int k) __attribute__((always_inline)) {
+        if (k >= PER) return;
+        _Float16* base = reinterpret_cast<_Float16*>(ff_lds + 2 * buf * C::BUF) + srow * PW + 4 * g0 + 32 * k;
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        uint32_t hp[2], lp[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const f2 vv = { __uint_as_float(raw[k][2 * j]) * scale, __uint_as_float(raw[k][2 * j + 1]) * scale };
+            hp[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(vv, h2));
+            float r0, r1;
+            mx_remainder(hp[j], vv[0], vv[1], r0, r1);
+            const f2 rem = { r0, r1 };
+            lp[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(rem, h2));
+        }
+        *reinterpret_cast<uint2*>(base) = make_uint2(hp[0], hp[1]);
+        *reinterpret_cast<uint2*>(base + C::BUF / 2) = make_uint2(lp[0], lp[1]);
+    };
+    auto commit_q = [&](int buf) __attribute__((always_inline)) {
+        if (QUIRK) {
+            const float qraw = static_cast<float>(qrs * qv);
+            float* qs = reinterpret_cast<float*>(ff_lds + C::QOFF) + buf * 64 + (tid & 31);
+            qs[0] = qraw;
+            qs[32] = -qraw;
+        }
+    };
+    // R: the window in buffer `buf` -> arow; `beside(kb)` runs after the products of slot kb
+    auto rowpass = [&](int buf, auto beside) __attribute__((always_inline)) {
+        const _Float16* base = reinterpret_cast<const _Float16*>(ff_lds + 2 * buf * C::BUF) + m * PW + wave * 32 + 8 * h;
+        const _Float16* lbase = base + C::BUF / 2;
+        mx_float16 a = zero;
+        mx_half8 x[3], xl[3], tq[3];
+#pragma unroll
+        for (int kb = 0; kb < 2 && kb < NKB; ++kb) {
+            x[kb] = *reinterpret_cast<const mx_half8*>(base + 16 * kb);
+            xl[kb] = *reinterpret_cast<const mx_half8*>(lbase + 16 * kb);
+        }
+        tq[0] = tlo(0);
+        tq[1] = tlo(1);
+#pragma unroll
+        for (int kb = 0; kb < RS; ++kb) {
+            if (kb + 2 < NKB) {
+                x[(kb + 2) % 3] = *reinterpret_cast<const mx_half8*>(base + 16 * (kb + 2));
+                xl[(kb + 2) % 3] = *reinterpret_cast<const mx_half8*>(lbase + 16 * (kb + 2));
+                tq[(kb + 2) % 3] = tlo(kb + 2);
+            }
+            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[kb % 3], th[kb], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[kb % 3], tq[kb % 3], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl[kb % 3], th[kb], a, 0, 0, 0);
+            asm volatile("" : "+a"(a));
+            beside(kb);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        arow = a;
+    };
+    // S: arow -> V (+ quirk), split into hi + lo, exchange with lane ^ 32 -> hl[hb] (fw_kernels.hpp: split_piece)
+    float sv[16];
+    auto split_piece = [&](int buf, int hb, int piece) __attribute__((always_inline)) {
+        const int hf = piece >> 2, sub = piece & 3;
+        uint32_t (&hp)[8] = hl[hb][0];
+        uint32_t (&lp)[8] = hl[hb][1];
+        if (sub == 0) {
+            if (QUIRK) {
+                const float* qs4 = reinterpret_cast<const float*>(ff_lds + C::QOFF) + buf * 64 + (m & 1) * 32 + 4 * h;
+#pragma unroll
+                for (int k = 2 * hf; k < 2 * hf + 2; ++k) {
+                    const float4 t4 = *reinterpret_cast<const float4*>(qs4 + 8 * k);
+                    sv[4 * k] = __builtin_fmaf(arow[4 * k], kFfRowUnscale, t4.x);
+                    sv[4 * k + 1] = __builtin_fmaf(arow[4 * k + 1], kFfRowUnscale, t4.y);
+                    sv[4 * k + 2] = __builtin_fmaf(arow[4 * k + 2], kFfRowUnscale, t4.z);
+                    sv[4 * k + 3] = __builtin_fmaf(arow[4 * k + 3], kFfRowUnscale, t4.w);
+                }
+            } else {
+#pragma unroll
+                for (int k = 8 * hf; k < 8 * hf + 8; ++k) sv[k] = arow[k] * kFfRowUnscale;
+            }
+        } else if (sub == 1 || sub == 2) {
+#pragma unroll
+            for (int k = 4 * hf + 2 * (sub - 1); k < 4 * hf + 2 * sub; ++k) {
+                typedef float f2 __attribute__((ext_vector_type(2)));
+                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+                const f2 vv = { sv[2 * k], sv[2 * k + 1] };
+                hp[k] = __builtin_bit_cast(uint32_t, __builtin_convertvector(vv, h2));
+                float r0, r1;
+                mx_remainder(hp[k], vv[0], vv[1], r0, r1);
+                const f2 rem = { r0, r1 };
+                lp[k] = __builtin_bit_cast(uint32_t, __builtin_convertvector(rem, h2));
+            }
+        } else {
+            fx_swap4(hp[4 * hf], hp[4 * hf + 2], hp[4 * hf + 1], hp[4 * hf + 3], lp[4 * hf], lp[4 * hf + 2], lp[4 * hf + 1], lp[4 * hf + 3]);
+        }
+    };
+    // E + F: rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column of the finished tile -> f32, stored at once.  Buffer stores: rows
+    // past the image, pixels right of it and tiles that do not exist get an offset outside the resource
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows) * g.cols * static_cast<uint32_t>(4 * CH), kMxRsrcWord3);
+    const uint32_t rowstep = 4u * static_cast<uint32_t>(g.cols) * CH;
+    const int xcol = x0 + 32 * wave + m;
+    auto emit_store = [&](int tile, bool valid, int gq) __attribute__((always_inline)) {
+        const int row0 = 32 * tile + 8 * gq + 4 * h;
+        const uint32_t base = 4u * ((static_cast<uint32_t>(row0) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int reg = 4 * gq + k;
+            const float v = __builtin_fmaf(tfin[reg] * kMxUnscale, unscale, (reg & 1) ? cneg : cpos);
+            const bool ok = valid && xcol < g.cols && row0 + k < g.rows;
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, ok ? base + k * rowstep : 0xfffffff0u, 0, 0);
+        }
+    };
+    auto colpass = [&](int qs, int hb, int ri, auto beside) __attribute__((always_inline)) {
+        mx_half8 v1[2], v2[2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const u4 w1 = { hl[hb][0][4 * b], hl[hb][0][4 * b + 1], hl[hb][0][4 * b + 2], hl[hb][0][4 * b + 3] };
+            const u4 w2 = { hl[hb][1][4 * b], hl[hb][1][4 * b + 1], hl[hb][1][4 * b + 2], hl[hb][1][4 * b + 3] };
+            v1[b] = __builtin_bit_cast(mx_half8, w1);
+            v2[b] = __builtin_bit_cast(mx_half8, w2);
+        }
+        auto dof = [](int it) { return it == 0 ? NKB - 1 : (it >= NKB - 2 ? it - (NKB - 2) : it + 1); };
+        mx_half8 tq[3];
+        tq[0] = tlo(dof(0));
+        if (NKB > 1) tq[1] = tlo(dof(1));
+#pragma unroll
+        for (int it = 0; it < CS; ++it) {
+            if (it < NKB) {
+                const int d = dof(it);
+                const int b = d & 1, a2 = d >> 1, slot = (qs - a2 + 2 * NT) % NT;
+                if (it + 2 < NKB) tq[(it + 2) % 3] = tlo(dof(it + 2));
+                if (ri < 0 || a2 <= ri) {
+                    mx_float16 t = d == 0 ? zero : acc[slot];
+                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[d], v1[b], t, 0, 0, 0);
+                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(tq[it % 3], v1[b], t, 0, 0, 0);
+                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[d], v2[b], t, 0, 0, 0);
+                    asm volatile("" : "+a"(t));
+                    if (it == 0) tfin = t; else acc[slot] = t;
+                }
+            }
+            beside(it);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+
+    // prologue: windows s0 and s0 + 1 in LDS, the first row pass and its hand-off done
+    issue_window(s0);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) commit_item(0, k);
+    commit_q(0);
+    issue_window(s0 + 1);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) commit_item(1, k);
+    commit_q(1);
+    __syncthreads();
+    rowpass(0, [](int) {});
+#pragma unroll
+    for (int p = 0; p < 8; ++p) split_piece(0, 0, p);
+    __syncthreads();
+
+    // step s: the row pass of step s + 1, then the column pass of step s (which finishes tile s - NT), the vector work beside the products
+    auto step = [&](int s, int qs, int ri) __attribute__((always_inline)) {
+        const int par = (s - s0) & 1;
+        const int ftile = s - NT;
+        const bool fvalid = ftile >= tile0;
+        issue_window(s + 2);
+        rowpass(par ^ 1, [](int) {});
+        colpass(qs, 0, ri, [&](int it) __attribute__((always_inline)) {
+            if (it < 8) split_piece(par ^ 1, 1, it);
+            if (it >= 1 && it <= 4) emit_store(ftile, fvalid, it - 1);
+            if (it >= 5) {
+#pragma unroll
+                for (int i = 0; i < IPS; ++i) commit_item(par, IPS * (it - 5) + i);
+            }
+            if (it == CS - 1) commit_q(par);
+        });
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { hl[0][0][k] = hl[1][0][k]; hl[0][1][k] = hl[1][1][k]; }
+        __syncthreads();                                   // window s + 2 complete, window s + 1 no longer read
+    };
+#pragma unroll
+    for (int j = 0; j < NT; ++j) step(s0 + j, j, j);
+    for (int sb = s0 + NT; sb < s1; sb += NT) {
+#pragma unroll
+        for (int qs = 0; qs < NT; ++qs) {
+            const int s = sb + qs;
+            if (s >= s1) break;
+            step(s, qs, -1);
+        }
+    }
+}
+
+// The classes that are instantiated: all but NKB = 23 with 3 or 4 channels, whose strided loads leave no registers for the window
+// (768 bytes of scratch per lane); those take the plane fallback
+__host__ __device__ constexpr bool ff_class_ok(int nkb, int ch) { return !(nkb >= 23 && ch != 1); }
+
+struct FfEntry {
+    int nkb;
+    // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (qk.mbits always is)
+    hipError_t (*blur_f32)(hipStream_t, const float* src, float* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk,
+                           const float* strips);
+};
+
+template <int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const float* src, float* dst, const void* frags, FxGeom g, int num_cus, const FfQuirk& qk,
+                                                   bool quirk, const float* strips)
+{
+    using C = FfCfg<NKB>;
+    const int chunks = (g.cols + kFxChunk - 1) / kFxChunk;
+    const long long nstripes = static_cast<long long>(chunks) * g.nframes * CH;       // (strip of columns, channel)
+    if (nstripes <= 0) return hipSuccess;
+    // segments per strip as in fw_launch_u8: the shortest makespan = rounds x (tiles per segment + NT of run-in).  (The segments
+    // change no result: every output tile sums its products in the same order in any segment.)
+    int nseg = 1, tps = g.ntiles;
+    {
+        long long best = -1;
+        for (int n = 1; n <= g.ntiles; ++n) {
+            const int t = (g.ntiles + n - 1) / n, ns = (g.ntiles + t - 1) / t;
+            const long long rounds = (nstripes * ns + num_cus - 1) / num_cus, span = rounds * (t + C::NT);
+            if (best < 0 || span < best) { best = span; nseg = ns; tps = t; }
+        }
+    }
+    const long long ntasks = nstripes * nseg;
+    if (g.nxcd < 1) g.nxcd = 1;
+    const int per_xcd = static_cast<int>((ntasks + g.nxcd - 1) / g.nxcd);
+    const dim3 grid(static_cast<unsigned>(g.nxcd * per_xcd));
+    static std::atomic<unsigned long long> attr_done{ 0 };
+    int dev;
+    if (fx_attr_needed(attr_done, dev)) {
+        const void* kernels[2] = { reinterpret_cast<const void*>(ff_blur_f32<NKB, true, CH>), reinterpret_cast<const void*>(ff_blur_f32<NKB, false, CH>) };
+        for (const void* k : kernels) {
+            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+            if (e != hipSuccess) return e;
+        }
+        fx_attr_mark(attr_done, dev);
+    }
+    if (quirk)
+        hipLaunchKernelGGL((ff_blur_f32<NKB, true, CH>), grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, chunks, tps, nseg,
+                           static_cast<int>(ntasks), qk, strips);
+    else
+        hipLaunchKernelGGL((ff_blur_f32<NKB, false, CH>), grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, chunks, tps, nseg,
+                           static_cast<int>(ntasks), qk, strips);
+    return hipGetLastError();
+}
+
+template <int NKB> hipError_t ff_launch_f32(hipStream_t st, const float* src, float* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk,
+                                            bool quirk, const float* strips)
+{
+    if (ch == 1) return ff_launch_ch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
+    if constexpr (ff_class_ok(NKB, 3)) {
+        if (ch == 3) return ff_launch_ch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
+        if (ch == 4) return ff_launch_ch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
+    }
+    return hipErrorInvalidValue;
+}
+
+#define BLUR_FF(NKB_)                                                                                       \
+    namespace blur_amd {                                                                                    \
+    const FfEntry* ff_entry_##NKB_()                                                                        \
+    {                                                                                                       \
+        static const FfEntry e = { NKB_, ff_launch_f32<NKB_> };                                             \
+        return &e;                                                                                          \
+    }                                                                                                       \
+    }
+
+// ---- what runs before the fused kernel (engine.hip) ------------------------------------------------------------------
+// strips[f][strip][row][CH (128 + 2 pada)] floats: the window of an edge chunk with the mirrored pixels in place.  A thread moves
+// one float.
+template <int CH>
+__device__ __forceinline__ void ff_edge_strips_body(const float* __restrict__ src, float* __restrict__ strips, int rows, int cols, int pada, int chunks,
+                                                    int nright, int bx, int sidx, int f)
+{
+    const int win = kFxChunk + 2 * pada, fpr = CH * win;                // floats per strip row
+    const int nleft = fx_left_strips(pada);
+    const int xc = sidx < nleft ? sidx : chunks - nright + sidx - nleft, x0 = kFxChunk * xc;
+    const int i = bx * 256 + threadIdx.x;
+    if (i >= rows * fpr) return;
+    const int r = i / fpr, e = i - r * fpr, p = e / CH, ch = e - p * CH;
+    const float* line = src + (static_cast<size_t>(f) * rows + r) * cols * CH;
+    strips[((static_cast<size_t>(f) * (nleft + nright) + sidx) * rows + r) * fpr + e] = line[CH * mx_refl(x0 - pada + p, cols) + ch];
+}
+
+// The pre-pass's sums for a CH-channel float image: workgroup (band of band_rows rows, batch of G BS elements of a row, frame), BS =
+// 256 (CH = 1, 4) or 255 (CH = 3): element j BS + t of the batch belongs to thread t, so that all of a thread's elements are of
+// channel t mod CH.  Always: max|x| of the frame into mbits (integer atomicMax on the bits: order-free).  With `sums`: the parts of
+// Srow per batch (spart[f][batch][row][CH]) and the column sums per band (cpart), f32 products summed in double, every sum in a
+// fixed order.
+constexpr int kFfSumRows = 16;
+__host__ __device__ constexpr int ff_batch_stride(int ch) { return ch == 3 ? 255 : 256; }
+inline int ff_groups_per_thread(int cols, int ch)
+{
+    const int ne = cols * ch, bs = ff_batch_stride(ch);
+    return ne <= bs ? 1 : (ne <= 2 * bs ? 2 : 4);
+}
+
+template <int CH, int G>
+__device__ __forceinline__ void ff_altsums_body(const float* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
+                                                int rows, int cols, int pad, int nbands, int nbatches, int cpitch, int band, int batch, int f, int band_rows, bool sums)
+{
+    constexpr int BS = ff_batch_stride(CH);
+    __shared__ double red[kFfSumRows][256];
+    __shared__ double red2[kFfSumRows][16][CH];
+    __shared__ float wmax[4];
+    const int tid = threadIdx.x;
+    const uint32_t ne = static_cast<uint32_t>(cols) * CH;
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src + static_cast<size_t>(f) * rows * ne), 0,
+                                                                          static_cast<uint32_t>(rows) * ne * 4u, kMxRsrcWord3);
+    const int r0 = band * band_rows, r1 = min(r0 + band_rows, rows);
+    int dj[G], wx[G];
+    bool own[G];
+    double col[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        dj[j] = (batch * G + j) * BS + tid;
+        own[j] = tid < BS && dj[j] < static_cast<int>(ne);
+        wx[j] = own[j] ? mx_alt_weight(dj[j] / CH, cols, pad) : 0;
+        col[j] = 0.0;
+    }
+    float amax = 0.f;
+    for (int rs = r0; rs < r1; rs += kFfSumRows) {
+        const int re = min(rs + kFfSumRows, r1);
+#pragma unroll 4
+        for (int r = rs; r < re; ++r) {
+            float v[G];
+#pragma unroll
+            for (int j = 0; j < G; ++j)
+                v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rimg, own[j] ? 4u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
+#pragma unroll
+            for (int j = 0; j < G; ++j) amax = fmaxf(amax, fabsf(v[j]));
+            if (sums) {
+                const int wy = mx_alt_weight(r, rows, pad);
+                double s = 0.0;
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    s = __builtin_fma(static_cast<double>(wx[j]), static_cast<double>(v[j]), s);
+                    col[j] = __builtin_fma(static_cast<double>(wy), static_cast<double>(v[j]), col[j]);
+                }
+                red[r - rs][tid] = s;
+            }
+        }
+        if (!sums) continue;
+        __syncthreads();
+        {   // thread (row, part): the 16 entries of its part, by channel; then the 16 parts of (row, channel) in order
+            const int rr = tid >> 4, part = tid & 15;
+            double pc[CH];
+#pragma unroll
+            for (int ch = 0; ch < CH; ++ch) pc[ch] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int t = 16 * part + k;
+                if (t < BS) pc[t % CH] += red[rr][t];
+            }
+#pragma unroll
+            for (int ch = 0; ch < CH; ++ch) red2[rr][part][ch] = pc[ch];
+        }
+        __syncthreads();
+        if (tid < (re - rs) * CH) {
+            const int rr = tid / CH, ch = tid - rr * CH;
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v += red2[rr][k][ch];
+            spart[((static_cast<size_t>(f) * nbatches + batch) * rows + rs + rr) * CH + ch] = v;
+        }
+        __syncthreads();
+    }
+    if (sums) {
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+            if (own[j]) cpart[(static_cast<size_t>(f) * nbands + band) * cpitch + dj[j]] = col[j];
+    }
+    // the workgroup's max|x| (NaN: the largest bits) -> one integer atomicMax
+    unsigned mb = __float_as_uint(amax);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mb = max(mb, static_cast<unsigned>(__shfl_xor(static_cast<int>(mb), o)));
+    if ((tid & 63) == 0) wmax[tid >> 6] = __uint_as_float(mb);
+    __syncthreads();
+    if (tid == 0) {
+        unsigned m4 = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) m4 = max(m4, __float_as_uint(wmax[w]));
+        atomicMax(mbits + f, m4);
+    }
+}
+
+// One launch: the max and (with sums) the quirk's parts (n_alt = bands x batches x frames workgroups), then the edge strips
+// (strip_blocks x nstrips x frames workgroups).  mbits must be zero before the launch.
+template <int CH, int G>
+__global__ __launch_bounds__(256) void ff_prepass(const float* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
+                                                  float* __restrict__ strips, int rows, int cols, int pad, int pada, int nbands, int nbatches, int cpitch, int n_alt,
+                                                  int chunks, int nright, int strip_blocks, int band_rows, int sums)
+{
+    int b = blockIdx.x;
+    if (b < n_alt) {
+        const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
+        ff_altsums_body<CH, G>(src, mbits, spart, cpart, rows, cols, pad, nbands, nbatches, cpitch, band, batch, f, band_rows, sums != 0);
+    } else {
+        b -= n_alt;
+        const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);
+        ff_edge_strips_body<CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f);
+    }
+}
+
+// Srow complete (the batches' parts in order) and Z = sum_r wy(r) Srow(r) (a fixed tree): one workgroup per frame
+template <int CH>
+__global__ __launch_bounds__(256) void ff_finalize(const double* __restrict__ spart, double* __restrict__ srow, double* __restrict__ zsum, int rows, int pad, int nbatches)
+{
+    __shared__ double zr[CH][256];
+    const int tid = threadIdx.x, f = blockIdx.x;
+    double z[CH];
+#pragma unroll
+    for (int ch = 0; ch < CH; ++ch) z[ch] = 0.0;
+    for (int r = tid; r < rows; r += 256) {
+        const double wy = static_cast<double>(mx_alt_weight(r, rows, pad));
+#pragma unroll
+        for (int ch = 0; ch < CH; ++ch) {
+            double s = 0.0;
+            for (int b = 0; b < nbatches; ++b) s += spart[((static_cast<size_t>(f) * nbatches + b) * rows + r) * CH + ch];
+            srow[(static_cast<size_t>(f) * rows + r) * CH + ch] = s;
+            z[ch] = __builtin_fma(wy, s, z[ch]);
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < CH; ++ch) zr[ch][tid] = z[ch];
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w)
+#pragma unroll
+            for (int ch = 0; ch < CH; ++ch) zr[ch][tid] += zr[ch][tid + w];
+        __syncthreads();
+    }
+    if (tid < CH) zsum[static_cast<size_t>(f) * CH + tid] = zr[tid][0];
+}
+
+}  // namespace blur_amd

@@ -124,8 +124,8 @@ int blur_ctx_synchronize(blur_ctx* ctx);
 const char* blur_last_error(const blur_ctx* ctx);
 /* which kernels the last u8c3 blur (or blur_gaussian_u8_*) on this ctx ran on: returns 0 run-time-planned FFT, 1 specialised rows-first
    FFT, 2 wave-resident FFT, 3 whole-image 2D FFT, 4 two-kernel matrix-core engine, 6 fused matrix-core kernel, 7 tiled wave-resident
-   FFT (-1: none yet); 1- and 4-channel images report 6 (their fused kernel) or 0 (the plane fallback), and it writes into note
-   (n bytes, may be NULL) the engine's name and, under BLUR_ENGINE_AUTO, why a faster engine was passed over -- e.g.
+   FFT (-1: none yet); 1- and 4-channel u8 images and float32 images report 6 (their fused kernel) or 0 (the plane fallback), and it
+   writes into note (n bytes, may be NULL) the engine's name and, under BLUR_ENGINE_AUTO, why a faster engine was passed over -- e.g.
    "two-kernel matrix-core engine (not taken: wide fused kernel (pad 73 .. 168): frames below 1 MP run on two kernels or the FFT kernels)" */
 int blur_last_engine(const blur_ctx* ctx, char* note, size_t n);
 
@@ -172,6 +172,27 @@ int blur_gaussian_u8_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, in
 /* the same for one frame in HOST memory: copy in, blur, copy out, synchronise */
 int blur_gaussian_u8_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, int channels, double sigma,
                           const blur_opts* opts);
+
+/* float32 frames of 1, 3 or 4 channels, interleaved, rows*cols*channels floats per frame, nframes back to back, DEVICE pointers
+   (4-byte aligned; any float offset).  Every channel is blurred on its own exactly as pffft_() blurs one of its planes (sizing and
+   kernel from (rows, cols, sigma), reflect-101, the Nyquist-slot quirk per channel plane unless opts->nyquist_quirk = 0) and the
+   result is the float plane as blur_gaussian_f32c1_dev returns it: no + 0.5f truncation, no clamping.  Parity: |got - float64
+   reference| <= 1e-6 max|x| of the frame, per pixel and channel.  opts->engine AUTO takes the fused matrix-core kernel wherever it
+   applies (pad <= 168; pad 153 .. 168 for 1 channel only; frames of at most 4 GiB - 4 KiB), the f32 plane path per channel
+   elsewhere; FUSED fails with BLUR_ERR_UNSUPPORTED where the fused kernel does not apply; FFT always takes the plane path; other
+   engines are BLUR_ERR_UNSUPPORTED.  blur_last_engine reports 6 (fused) or 0 (plane path).  The call is asynchronous on the
+   context's stream.  Results are bit-reproducible: a frame gives the same bits alone and inside a batch.  d_dst may equal d_src;
+   other overlaps are detected over the whole batch and read from a copy.  Inputs holding NaN or +-Inf give unspecified output
+   values (no kernel reads or writes outside its buffers).  BLUR_ERR_INVALID: channels not in {1, 3, 4}, a NULL pointer,
+   nframes < 0, rows, cols or sigma <= 0; BLUR_ERR_UNSUPPORTED: pad > min(rows, cols) - 1.  These are checked before the device is
+   touched (ctx may then be NULL); nframes == 0 is a no-op. */
+int blur_gaussian_f32_batch_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels,
+                                double sigma, const blur_opts* opts);
+int blur_gaussian_f32_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int channels, double sigma,
+                          const blur_opts* opts);
+/* the same for one frame in HOST memory: copy in, blur, copy out, synchronise */
+int blur_gaussian_f32_host(blur_ctx* ctx, const float* src, float* dst, int rows, int cols, int channels, double sigma,
+                           const blur_opts* opts);
 
 /* HOST pointers: copy in, blur, copy out, synchronise (what a cv::Mat caller needs). */
 int blur_gaussian_u8c3_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst,
@@ -302,6 +323,11 @@ int blur_gaussian_u8_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint8_
                                      double sigma, const blur_opts* opts);
 int blur_gaussian_u8_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, int channels,
                                       double sigma, const blur_opts* opts);
+/* blur_gaussian_f32_batch_dev over a batch, sharded by frame exactly like the calls above */
+int blur_gaussian_f32_batch_multi_dev(blur_multi* m, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels,
+                                      double sigma, const blur_opts* opts);
+int blur_gaussian_f32_batch_multi_host(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels,
+                                       double sigma, const blur_opts* opts);
 /* fastboxblur over a batch, sharded by frame exactly like the two calls above, in place (blur_fastboxblur_u8_batch_dev on
    each shard); arguments and errors as blur_fastboxblur_u8_batch_dev, nframes == 0 is a no-op, shards without frames idle. */
 int blur_fastboxblur_u8_batch_multi_dev(blur_multi* m, uint8_t* d_inout, int nframes, int w, int h, int channels,

@@ -221,6 +221,14 @@ template <class Mat, class = decltype(std::declval<Mat&>().channels())> void gau
     gaussian_blur(reinterpret_cast<uint8_t*>(image.data), static_cast<int>(image.size[0]), static_cast<int>(image.size[1]), static_cast<int>(image.channels()), sigma);
 }
 
+// gaussian_blur for float32 images of 1, 3 or 4 channels, in place: every channel blurred on its own as pffft_ blurs one of its
+// planes, without the + 0.5f truncation (blur_gaussian_f32_host)
+inline void gaussian_blur(float* data, int rows, int cols, int channels, double sigma, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f32_host(ctx, data, data, rows, cols, channels, sigma, opts), "gaussian_blur");
+}
+
 // pocketfft_1D(image, sigma) (Source.cpp:280-392) and pocketfft_2D(image, sigma) (Source.cpp:143-277): the two
 // pocketfft paths multiply all N/2+1 bins with the kernel's own spectrum (no Nyquist-slot quirk) and, inside the
 // cropped image, both equal the linear convolution of the reflect-101 extended image -- the engine's
