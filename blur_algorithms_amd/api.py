@@ -104,22 +104,7 @@ def _box_frames_shape(shape):
 
 
 def _gauss_frames_shape(shape):
-    """[rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4} -> (n, rows, cols, C)"""
-    if len(shape) == 2:
-        n, rows, cols, ch = 1, shape[0], shape[1], 1
-    elif len(shape) == 3:
-        n, (rows, cols, ch) = 1, shape
-    elif len(shape) == 4:
-        n, rows, cols, ch = shape
-    else:
-        n = ch = 0
-    if ch not in (1, 3, 4):
-        raise ValueError("expected uint8 [rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4}")
-    return n, rows, cols, ch
-
-
-def _gauss_f32_frames_shape(shape):
-    """float32 [rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4} -> (n, rows, cols, C)"""
+    """[rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4} and rows, cols > 0 -> (n, rows, cols, C)"""
     if len(shape) == 2:
         n, rows, cols, ch = 1, shape[0], shape[1], 1
     elif len(shape) == 3:
@@ -129,8 +114,43 @@ def _gauss_f32_frames_shape(shape):
     else:
         n = rows = cols = ch = 0
     if ch not in (1, 3, 4) or rows <= 0 or cols <= 0:
-        raise ValueError("expected float32 [rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4}")
+        raise ValueError("expected [rows, cols], [rows, cols, C] or [n, rows, cols, C] with C in {1, 3, 4}")
     return n, rows, cols, ch
+
+
+_gauss_f32_frames_shape = _gauss_frames_shape      # (the float32 entry points' name for the same helper)
+
+
+def _gauss_array(image, out, dtype, batch=False):
+    """the host arrays of a per-channel Gaussian call: (source, result, (n, rows, cols, C)).  uint8 input of another dtype is
+    converted, as pffft_ does; float32 input must be float32.  batch: frames [n, rows, cols, C] only"""
+    if dtype == np.float32 and image.dtype != np.float32:
+        raise ValueError("expected a float32 array")
+    a = np.ascontiguousarray(image, dtype)
+    if batch and a.ndim != 4:
+        raise ValueError("expected %s frames [n, rows, cols, C]" % np.dtype(dtype).name)
+    shape = _gauss_frames_shape(a.shape)
+    res = np.empty_like(a) if out is None else out
+    if not isinstance(res, np.ndarray) or res.shape != a.shape or res.dtype != a.dtype or not res.flags["C_CONTIGUOUS"]:
+        raise ValueError("out must match the input")
+    return a, res, shape
+
+
+def _gauss_tensor(image, out, dtype, device=None):
+    """the CUDA tensors of a per-channel Gaussian call: (source, result (default: the source), (n, rows, cols, C)).  device: frames
+    [n, rows, cols, C] on that device only"""
+    import torch
+    want = torch.uint8 if dtype == np.uint8 else torch.float32
+    t = image
+    if (not isinstance(t, torch.Tensor) or t.dtype != want or not t.is_cuda or not t.is_contiguous()
+            or (device is not None and (t.dim() != 4 or t.device.index != device))):
+        layout = "[rows, cols], [rows, cols, C] or [n, rows, cols, C]" if device is None else "[n, rows, cols, C] on devices[0]"
+        raise ValueError("expected a contiguous CUDA %s tensor %s" % (np.dtype(dtype).name, layout))
+    shape = _gauss_frames_shape(tuple(t.shape))
+    dst = t if out is None else out
+    if not isinstance(dst, torch.Tensor) or dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
+        raise ValueError("out must match the input")
+    return t, dst, shape
 
 
 def fft_plan_radices(n):
@@ -471,29 +491,7 @@ class BlurContext:
         torch CUDA tensor: asynchronous on torch's current stream, returns `out` (default: in place, like pffft_).  numpy array:
         host round trip, returns a new array.
         """
-        o = self._opts(nyquist_quirk, engine=engine)
-        if isinstance(image, np.ndarray):
-            a = np.ascontiguousarray(image, np.uint8)
-            n, rows, cols, ch = _gauss_frames_shape(a.shape)
-            res = np.empty_like(a) if out is None else out
-            if res.shape != a.shape or res.dtype != np.uint8 or not res.flags["C_CONTIGUOUS"]:
-                raise ValueError("out must match the input")
-            fb = rows * cols * ch
-            for f in range(n):
-                self._check(self._lib.blur_gaussian_u8_host(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch,
-                                                            float(sigma), C.byref(o)))
-            return res
-        import torch
-        t = image
-        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("expected a contiguous CUDA uint8 tensor [rows, cols], [rows, cols, C] or [n, rows, cols, C]")
-        n, rows, cols, ch = _gauss_frames_shape(tuple(t.shape))
-        dst = t if out is None else out
-        if dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
-            raise ValueError("out must match the input")
-        self.use_torch_stream()
-        self._check(self._lib.blur_gaussian_u8_batch_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
-        return dst
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.uint8, self._lib.blur_gaussian_u8_host, self._lib.blur_gaussian_u8_batch_dev)
 
     def gaussian_f32(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
         """Gaussian blur of a float32 image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows, cols, C].  Every
@@ -503,30 +501,20 @@ class BlurContext:
         torch CUDA tensor: asynchronous on torch's current stream, returns `out` (default: in place).  numpy array: host round trip,
         returns a new array.
         """
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.float32, self._lib.blur_gaussian_f32_host,
+                              self._lib.blur_gaussian_f32_batch_dev)
+
+    def _gaussian(self, image, sigma, out, nyquist_quirk, engine, dtype, host_entry, batch_dev_entry):
         o = self._opts(nyquist_quirk, engine=engine)
         if isinstance(image, np.ndarray):
-            if image.dtype != np.float32:
-                raise ValueError("expected a float32 array")
-            a = np.ascontiguousarray(image)
-            n, rows, cols, ch = _gauss_f32_frames_shape(a.shape)
-            res = np.empty_like(a) if out is None else out
-            if res.shape != a.shape or res.dtype != np.float32 or not res.flags["C_CONTIGUOUS"]:
-                raise ValueError("out must match the input")
-            fb = rows * cols * ch * 4
+            a, res, (n, rows, cols, ch) = _gauss_array(image, out, dtype)
+            fb = rows * cols * ch * a.itemsize
             for f in range(n):
-                self._check(self._lib.blur_gaussian_f32_host(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch,
-                                                             float(sigma), C.byref(o)))
+                self._check(host_entry(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch, float(sigma), C.byref(o)))
             return res
-        import torch
-        t = image
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("expected a contiguous CUDA float32 tensor [rows, cols], [rows, cols, C] or [n, rows, cols, C]")
-        n, rows, cols, ch = _gauss_f32_frames_shape(tuple(t.shape))
-        dst = t if out is None else out
-        if dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
-            raise ValueError("out must match the input")
+        t, dst, (n, rows, cols, ch) = _gauss_tensor(image, out, dtype)
         self.use_torch_stream()
-        self._check(self._lib.blur_gaussian_f32_batch_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
+        self._check(batch_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
         return dst
 
     def fastboxblur(self, image, ksize, passes):
@@ -617,58 +605,29 @@ class BlurMulti:
     def gaussian(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
         """BlurContext.gaussian over a batch sharded by frame: frames uint8 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
         tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
-        o = BlurOpts()
-        self._lib.blur_opts_default(C.byref(o))
-        o.nyquist_quirk = 1 if nyquist_quirk else 0
-        if engine is not None:
-            o.engine = ENGINES[engine]
-        if isinstance(frames, np.ndarray):
-            a = np.ascontiguousarray(frames, np.uint8)
-            if a.ndim != 4:
-                raise ValueError("expected uint8 frames [n, rows, cols, C]")
-            n, rows, cols, ch = _gauss_frames_shape(a.shape)
-            res = np.empty_like(a) if out is None else out
-            self._check(self._lib.blur_gaussian_u8_batch_multi_host(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, float(sigma), C.byref(o)))
-            return res
-        import torch
-        t = frames
-        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.dim() != 4 or t.device.index != self.devices[0]:
-            raise ValueError("expected a contiguous CUDA uint8 tensor [n, rows, cols, C] on devices[0]")
-        n, rows, cols, ch = _gauss_frames_shape(tuple(t.shape))
-        dst = t if out is None else out
-        torch.cuda.synchronize(t.device)
-        self._check(self._lib.blur_gaussian_u8_batch_multi_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
-        return dst
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.uint8, self._lib.blur_gaussian_u8_batch_multi_host,
+                              self._lib.blur_gaussian_u8_batch_multi_dev)
 
     def gaussian_f32(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
         """BlurContext.gaussian_f32 over a batch sharded by frame: frames float32 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
         tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.float32, self._lib.blur_gaussian_f32_batch_multi_host,
+                              self._lib.blur_gaussian_f32_batch_multi_dev)
+
+    def _gaussian(self, frames, sigma, out, nyquist_quirk, engine, dtype, multi_host_entry, multi_dev_entry):
         o = BlurOpts()
         self._lib.blur_opts_default(C.byref(o))
         o.nyquist_quirk = 1 if nyquist_quirk else 0
         if engine is not None:
             o.engine = ENGINES[engine]
         if isinstance(frames, np.ndarray):
-            if frames.dtype != np.float32 or frames.ndim != 4:
-                raise ValueError("expected float32 frames [n, rows, cols, C]")
-            a = np.ascontiguousarray(frames)
-            n, rows, cols, ch = _gauss_f32_frames_shape(a.shape)
-            res = np.empty_like(a) if out is None else out
-            if res.shape != a.shape or res.dtype != np.float32 or not res.flags["C_CONTIGUOUS"]:
-                raise ValueError("out must match the input")
-            self._check(self._lib.blur_gaussian_f32_batch_multi_host(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, float(sigma), C.byref(o)))
+            a, res, (n, rows, cols, ch) = _gauss_array(frames, out, dtype, batch=True)
+            self._check(multi_host_entry(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, float(sigma), C.byref(o)))
             return res
         import torch
-        t = frames
-        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 4
-                or t.device.index != self.devices[0]):
-            raise ValueError("expected a contiguous CUDA float32 tensor [n, rows, cols, C] on devices[0]")
-        n, rows, cols, ch = _gauss_f32_frames_shape(tuple(t.shape))
-        dst = t if out is None else out
-        if dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
-            raise ValueError("out must match the input")
+        t, dst, (n, rows, cols, ch) = _gauss_tensor(frames, out, dtype, device=self.devices[0])
         torch.cuda.synchronize(t.device)
-        self._check(self._lib.blur_gaussian_f32_batch_multi_dev(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
+        self._check(multi_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
         return dst
 
     def fastboxblur(self, frames, ksize, passes):

@@ -26,6 +26,7 @@
 #include <memory>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/blur_amd.h"
@@ -1698,9 +1699,11 @@ static int run_colpass_u8c3(blur_ctx* ctx, const float* planes, uint8_t* dst, in
 }
 
 // ======================================================================================
-// 1- and 4-channel u8 images (blur_gaussian_u8_*): every channel blurred on its own as pffft_() blurs one of its three
+// 1- and 4-channel u8 images (blur_gaussian_u8_*) and float32 images of 1, 3 or 4 channels (blur_gaussian_f32_*): every channel
+// blurred on its own as pffft_() blurs one of its planes (u8 with the + 0.5f truncation, float32 without)
 // ======================================================================================
 #include "fc_registry.hpp"
+#include "ff_registry.hpp"
 
 static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
 {
@@ -1717,7 +1720,7 @@ static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
 }
 
 // the fused kernel for CH = 1, 4 (fc_kernels.hpp): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
-// Frames are disjoint from the destination here (blur_u8_batch_impl copies overlapping ones first).
+// Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).
 static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
 {
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
@@ -1769,130 +1772,8 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
     return BLUR_OK;
 }
 
-// the plane fallback: split a frame into f32 planes, blur each on the f32 plane path, pack with + 0.5f truncation
-__global__ void chan_split_u8_f32(const uint8_t* __restrict__ src, float* __restrict__ planes, size_t px, int ch)
-{
-    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        for (int c = 0; c < ch; ++c) planes[c * px + i] = static_cast<float>(src[i * ch + c]);
-}
-
-__global__ void chan_pack_f32_u8(const float* __restrict__ planes, uint8_t* __restrict__ dst, size_t px, int ch)
-{
-    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        for (int c = 0; c < ch; ++c)       // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
-            dst[i * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffu);
-}
-
-static int run_planes_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts)
-{
-    Prepared p;
-    if (int rc = prepare(ctx, rows, cols, sigma, opts, p, false)) return rc;
-    const size_t px = static_cast<size_t>(rows) * cols;
-    if (int rc = ensure_work(ctx, px * sizeof(float))) return rc;
-    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_planes), &ctx->ch_planes_bytes, px * ch * sizeof(float))) return rc;
-    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((px + 255) / 256, 4096));
-    for (int f = 0; f < nframes; ++f) {
-        const uint8_t* s = d_src + static_cast<size_t>(f) * px * ch;
-        uint8_t* d = d_dst + static_cast<size_t>(f) * px * ch;
-        hipLaunchKernelGGL(chan_split_u8_f32, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch);
-        HIP_TRY(ctx, hipGetLastError());
-        for (int c = 0; c < ch; ++c) {
-            float* plane = ctx->ch_planes + c * px;
-            if (int rc = launch_rowpass<float, 1>(ctx, plane, ctx->work, rows, cols, p.sz.pad, *p.row, p.m_row)) return rc;
-            if (int rc = launch_colpass<float, 1>(ctx, ctx->work, plane, rows, cols, p.sz.pad, *p.col, p.m_col, p.col_group)) return rc;
-        }
-        hipLaunchKernelGGL(chan_pack_f32_u8, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return BLUR_OK;
-}
-
-static int blur_u8_batch_impl(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
-                              const blur_opts* opts)
-{
-    // the arguments first, without the device (ctx may be NULL here: the status is the same)
-    if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
-    if (!d_src || !d_dst || nframes < 0) return fail(ctx, BLUR_ERR_INVALID, "null frame pointer or negative frame count");
-    if (rows <= 0 || cols <= 0 || !(sigma > 0)) return fail(ctx, BLUR_ERR_INVALID, "rows, cols and sigma must be positive");
-    {
-        const Sizing sz = pffft_sizing(rows, cols, sigma);
-        if (sz.pad > rows - 1 || sz.pad > cols - 1)
-            return fail(ctx, BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1: reflect-101 would read outside the image (README.md:33-38)");
-    }
-    if (!ctx) return BLUR_ERR_INVALID;
-    if (channels == 3) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
-    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
-    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, "1- and 4-channel images: engine must be AUTO, FUSED or FFT");
-    // The fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED: a kernel for the pad, the frame and quirk limits),
-    // the plane fallback elsewhere.  AUTO too: where the u8c3 policy passes the fused engine over for a compile-time FFT family (frames
-    // under 1 MP, pad > 152 on 6 MP), the alternative here is the run-time-planned plane path, three to four times slower than the
-    // fused kernel (4K sigma 50, 8 frames: 0.146 ms per 1-channel frame, 0.568 per 4-channel one, on the plane path)
-    Prepared p;
-    std::string note;
-    if (choice != BLUR_ENGINE_FFT) {
-        blur_opts fo;
-        blur_opts_default(&fo);
-        if (opts) fo = *opts;
-        fo.engine = BLUR_ENGINE_FUSED;
-        const int rc = prepare(ctx, rows, cols, sigma, &fo, p, true);
-        if (rc == BLUR_ERR_UNSUPPORTED && choice == BLUR_ENGINE_AUTO) {
-            p = Prepared{};
-            note = ctx->err;
-            ctx->err.clear();                    // (not a failure of this call)
-        } else if (rc) return rc;
-        if (p.fx && static_cast<long long>(rows) * cols * channels > 0xfffff000ll) {
-            if (choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused matrix-core engine: frame too large for 32-bit offsets");
-            p.fx = nullptr;
-            note = "fused matrix-core engine: frame too large for 32-bit offsets";
-        }
-    }
-    if (nframes == 0) return BLUR_OK;
-    const size_t fb = static_cast<size_t>(rows) * cols * channels;
-    // overlap of the source and destination ranges (over the whole batch): the fused kernel reads its neighbours' pixels while it
-    // writes, and the plane path writes frame f before it reads frame f + 1.  An in-place call of the plane path needs no copy
-    // (frame f is read whole before it is written); every other overlap reads from a copy
-    const uint8_t* lo = d_src < d_dst ? d_src : d_dst;
-    const uint8_t* hi = d_src < d_dst ? d_dst : d_src;
-    const bool overlap = static_cast<size_t>(hi - lo) < fb * nframes;
-    if (overlap && (p.fx || d_src != d_dst)) {
-        if (d_src == d_dst) {       // in place: in parts of at most 1 GiB (a part's result never touches a later part's source)
-            const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
-            if (static_cast<size_t>(nframes) > cap) {
-                for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
-                    const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
-                    uint8_t* part = d_dst + static_cast<size_t>(f0) * fb;
-                    if (int rc = blur_u8_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts)) return rc;
-                }
-                return BLUR_OK;
-            }
-        }
-        if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
-        d_src = ctx->ch_copy;
-    }
-    if (p.fx) {
-        ctx->last_family = 6;
-        return run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
-    }
-    blur_opts o;
-    blur_opts_default(&o);
-    if (opts) o = *opts;
-    o.engine = BLUR_ENGINE_FFT;
-    if (int rc = run_planes_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, &o)) return rc;
-    ctx->last_family = 0;
-    ctx->engine_note = note;
-    return BLUR_OK;
-}
-
-// ======================================================================================
-// float32 images of 1, 3 or 4 channels (blur_gaussian_f32_*): every channel blurred on its own as pffft_() blurs one of its planes,
-// without the + 0.5f truncation
-// ======================================================================================
-#include "ff_registry.hpp"
-
 // the fused kernel (ff_kernels.hpp): the pre-pass (max|x|, the quirk's sums, the edge chunks' strips), the quirk's finalisation,
-// then the kernel.  Frames are disjoint from the destination here (blur_f32_batch_impl copies overlapping ones first).  Every
+// then the kernel.  Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).  Every
 // partition of a sum (bands, batches) depends on the frame's shape only: a frame gives the same bits alone and in a batch.
 static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
 {
@@ -1956,19 +1837,27 @@ static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nfram
 }
 
 // the plane fallback: split a frame into f32 planes, blur each on the f32 plane path, interleave the results
-__global__ void chan_split_f32(const float* __restrict__ src, float* __restrict__ planes, size_t px, int ch)
+template <typename T>
+__global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes, size_t px, int ch)
 {
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        for (int c = 0; c < ch; ++c) planes[c * px + i] = src[i * ch + c];
+        for (int c = 0; c < ch; ++c) planes[c * px + i] = static_cast<float>(src[i * ch + c]);
 }
 
-__global__ void chan_pack_f32(const float* __restrict__ planes, float* __restrict__ dst, size_t px, int ch)
+template <typename T>
+__global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst, size_t px, int ch)
 {
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        for (int c = 0; c < ch; ++c) dst[i * ch + c] = planes[c * px + i];
+        for (int c = 0; c < ch; ++c) {
+            if constexpr (std::is_same_v<T, uint8_t>)  // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
+                dst[i * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffu);
+            else
+                dst[i * ch + c] = planes[c * px + i];
+        }
 }
 
-static int run_planes_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts)
+template <typename T>
+static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts)
 {
     Prepared p;
     if (int rc = prepare(ctx, rows, cols, sigma, opts, p, false)) return rc;
@@ -1977,39 +1866,52 @@ static int run_planes_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int n
     if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_planes), &ctx->ch_planes_bytes, px * ch * sizeof(float))) return rc;
     const unsigned blocks = static_cast<unsigned>(std::min<size_t>((px + 255) / 256, 4096));
     for (int f = 0; f < nframes; ++f) {
-        const float* s = d_src + static_cast<size_t>(f) * px * ch;
-        float* d = d_dst + static_cast<size_t>(f) * px * ch;
-        hipLaunchKernelGGL(chan_split_f32, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch);
+        const T* s = d_src + static_cast<size_t>(f) * px * ch;
+        T* d = d_dst + static_cast<size_t>(f) * px * ch;
+        hipLaunchKernelGGL(chan_split<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch);
         HIP_TRY(ctx, hipGetLastError());
         for (int c = 0; c < ch; ++c) {
             float* plane = ctx->ch_planes + c * px;
             if (int rc = launch_rowpass<float, 1>(ctx, plane, ctx->work, rows, cols, p.sz.pad, *p.row, p.m_row)) return rc;
             if (int rc = launch_colpass<float, 1>(ctx, ctx->work, plane, rows, cols, p.sz.pad, *p.col, p.m_col, p.col_group)) return rc;
         }
-        hipLaunchKernelGGL(chan_pack_f32, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch);
+        hipLaunchKernelGGL(chan_pack<T>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch);
         HIP_TRY(ctx, hipGetLastError());
     }
     return BLUR_OK;
 }
 
-static int blur_f32_batch_impl(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, double sigma,
-                               const blur_opts* opts)
+// the arguments of every blur_gaussian_{u8,f32}_* entry, without the device (ctx may be NULL here: the status is the same)
+static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nframes, int rows, int cols, int channels, double sigma)
 {
-    // the arguments first, without the device (ctx may be NULL here: the status is the same)
     if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
-    if (!d_src || !d_dst || nframes < 0) return fail(ctx, BLUR_ERR_INVALID, "null frame pointer or negative frame count");
+    if (!src || !dst || nframes < 0) return fail(ctx, BLUR_ERR_INVALID, "null frame pointer or negative frame count");
     if (rows <= 0 || cols <= 0 || !(sigma > 0)) return fail(ctx, BLUR_ERR_INVALID, "rows, cols and sigma must be positive");
-    {
-        const Sizing sz = pffft_sizing(rows, cols, sigma);
-        if (sz.pad > rows - 1 || sz.pad > cols - 1)
-            return fail(ctx, BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1: reflect-101 would read outside the image (README.md:33-38)");
+    const Sizing sz = pffft_sizing(rows, cols, sigma);
+    if (sz.pad > rows - 1 || sz.pad > cols - 1)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1: reflect-101 would read outside the image (README.md:33-38)");
+    return ctx ? BLUR_OK : BLUR_ERR_INVALID;
+}
+
+// One driver for both element types.  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused kernel
+// for NKB 23 with 3 or 4 channels (ff_class_ok); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 /
+// run_ff_f32) and the engine error's text
+template <typename T>
+static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    constexpr bool f32 = std::is_same_v<T, float>;
+    if (int rc = check_ch_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma)) return rc;
+    if constexpr (!f32) {
+        if (channels == 3) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
     }
-    if (!ctx) return BLUR_ERR_INVALID;
     const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
     if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, "float32 images: engine must be AUTO, FUSED or FFT");
-    // the fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED, a class instantiated for the channel count, the
-    // frame's bytes within 32-bit offsets), the plane fallback elsewhere
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, f32 ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT");
+    // The fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED: a kernel for the pad, the frame and quirk limits; a
+    // float32 class instantiated for the channel count; the frame's bytes within 32-bit offsets), the plane fallback elsewhere.  AUTO
+    // too: where the u8c3 policy passes the fused engine over for a compile-time FFT family (frames under 1 MP, pad > 152 on 6 MP), the
+    // alternative here is the run-time-planned plane path, three to four times slower than the fused kernel (4K sigma 50, 8 frames:
+    // 0.146 ms per 1-channel u8 frame, 0.568 per 4-channel one, on the plane path)
     Prepared p;
     std::string note;
     if (choice != BLUR_ENGINE_FFT) {
@@ -2024,8 +1926,9 @@ static int blur_f32_batch_impl(blur_ctx* ctx, const float* d_src, float* d_dst, 
             ctx->err.clear();                    // (not a failure of this call)
         } else if (rc) return rc;
         const char* why = nullptr;
-        if (p.fx && !ff_class_ok(p.fx->nkb, channels)) why = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
-        else if (p.fx && static_cast<long long>(rows) * cols * channels * 4 > 0xfffff000ll) why = "fused matrix-core engine: frame too large for 32-bit offsets";
+        if (p.fx && f32 && !ff_class_ok(p.fx->nkb, channels)) why = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
+        else if (p.fx && static_cast<long long>(rows) * cols * channels * static_cast<long long>(sizeof(T)) > 0xfffff000ll)
+            why = "fused matrix-core engine: frame too large for 32-bit offsets";
         if (why) {
             if (choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, why);
             p.fx = nullptr;
@@ -2033,8 +1936,10 @@ static int blur_f32_batch_impl(blur_ctx* ctx, const float* d_src, float* d_dst, 
         }
     }
     if (nframes == 0) return BLUR_OK;
-    const size_t fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(float);
-    // overlap over the whole batch: as blur_u8_batch_impl
+    const size_t fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(T);
+    // overlap of the source and destination ranges (over the whole batch): the fused kernel reads its neighbours' pixels while it
+    // writes, and the plane path writes frame f before it reads frame f + 1.  An in-place call of the plane path needs no copy
+    // (frame f is read whole before it is written); every other overlap reads from a copy
     const char* lo = reinterpret_cast<const char*>(d_src < d_dst ? d_src : d_dst);
     const char* hi = reinterpret_cast<const char*>(d_src < d_dst ? d_dst : d_src);
     const bool overlap = static_cast<size_t>(hi - lo) < fb * nframes;
@@ -2044,28 +1949,48 @@ static int blur_f32_batch_impl(blur_ctx* ctx, const float* d_src, float* d_dst, 
             if (static_cast<size_t>(nframes) > cap) {
                 for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
                     const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
-                    float* part = d_dst + static_cast<size_t>(f0) * fe;
-                    if (int rc = blur_f32_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts)) return rc;
+                    T* part = d_dst + static_cast<size_t>(f0) * fe;
+                    if (int rc = blur_ch_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts)) return rc;
                 }
                 return BLUR_OK;
             }
         }
         if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
-        d_src = reinterpret_cast<const float*>(ctx->ch_copy);
+        d_src = reinterpret_cast<const T*>(ctx->ch_copy);
     }
     if (p.fx) {
         ctx->last_family = 6;
-        return run_ff_f32(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
+        if constexpr (f32) return run_ff_f32(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
+        else return run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
     }
     blur_opts o;
     blur_opts_default(&o);
     if (opts) o = *opts;
     o.engine = BLUR_ENGINE_FFT;
-    if (int rc = run_planes_f32(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, &o)) return rc;
+    if (int rc = run_planes(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, &o)) return rc;
     ctx->last_family = 0;
     ctx->engine_note = note;
     return BLUR_OK;
+}
+
+// blur_gaussian_{u8,f32}_host: one frame through the context's host staging buffer (source and destination apart: no in-place copy)
+template <typename T>
+static int blur_ch_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    if (int rc = check_ch_args(ctx, src, dst, 1, rows, cols, channels, sigma)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = static_cast<size_t>(rows) * cols * channels * sizeof(T), half = (bytes + 255) & ~static_cast<size_t>(255);
+    void* dv = nullptr;
+    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;
+    char* d = static_cast<char*>(dv);
+    int rc = BLUR_OK;
+    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) rc = blur_ch_batch_impl(ctx, reinterpret_cast<const T*>(d), reinterpret_cast<T*>(d + half), 1, rows, cols, channels, sigma, opts);
+    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
+    return rc;
 }
 
 // ======================================================================================
@@ -3378,39 +3303,10 @@ int blur_fastboxblur_u8_batch_multi_host(blur_multi* m, uint8_t* inout, int nfra
     return box_multi(m, inout, nframes, w, h, channels, ksize, passes, 0);
 }
 
-// 1-, 3- and 4-channel u8 images (channels == 3: the u8c3 entry points)
-int blur_gaussian_u8_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
-                               const blur_opts* opts)
-{
-    return blur_u8_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts);
-}
-
-int blur_gaussian_u8_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
-{
-    return blur_u8_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigma, opts);
-}
-
-int blur_gaussian_u8_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
-{
-    if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
-    if (!src || !dst || rows <= 0 || cols <= 0) return fail(ctx, BLUR_ERR_INVALID, "null image or non-positive size");
-    if (!ctx) return BLUR_ERR_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = static_cast<size_t>(rows) * cols * channels, half = (bytes + 255) & ~static_cast<size_t>(255);
-    void* dv = nullptr;
-    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;      // source and destination: no in-place copy
-    uint8_t* d = static_cast<uint8_t*>(dv);
-    int rc = BLUR_OK;
-    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) rc = blur_u8_batch_impl(ctx, d, d + half, 1, rows, cols, channels, sigma, opts);
-    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
-    return rc;
-}
-
-static int gaussian_u8_multi(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, int channels, double sigma,
-                             const blur_opts* opts, int location)
+// blur_gaussian_{u8,f32}_batch_multi_*: the frames of a batch sharded over the devices (a template: C++ linkage)
+extern "C++" {
+template <typename T>
+static int blur_ch_multi(blur_multi* m, const T* src, T* dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts, int location)
 {
     if (!m) return BLUR_ERR_INVALID;
     if (channels != 1 && channels != 3 && channels != 4) { m->err = "channels must be 1, 3 or 4"; return BLUR_ERR_INVALID; }
@@ -3418,85 +3314,70 @@ static int gaussian_u8_multi(blur_multi* m, const uint8_t* src, uint8_t* dst, in
     if (nframes == 0) return BLUR_OK;
     // frames queued by the caller on devices[0] must be complete before other devices (and other streams) read them
     if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
-    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels : 0;
-    return blur_multi_run(m, src, dst, nframes, fb, location, [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) {
-        return blur_u8_batch_impl(c, in, out, n, rows, cols, channels, sigma, opts);
-    });
+    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels * sizeof(T) : 0;
+    return blur_multi_run(m, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nframes, fb, location,
+                          [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) {
+                              return blur_ch_batch_impl(c, reinterpret_cast<const T*>(in), reinterpret_cast<T*>(out), n, rows, cols, channels, sigma, opts);
+                          });
+}
+}  // extern "C++"
+
+// 1-, 3- and 4-channel u8 images (channels == 3: the u8c3 entry points)
+int blur_gaussian_u8_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                               const blur_opts* opts)
+{
+    return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_u8_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_ch_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_u8_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_ch_host(ctx, src, dst, rows, cols, channels, sigma, opts);
 }
 
 int blur_gaussian_u8_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
                                      const blur_opts* opts)
 {
-    return gaussian_u8_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, 1);
+    return blur_ch_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, 1);
 }
 
 int blur_gaussian_u8_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, int channels, double sigma,
                                       const blur_opts* opts)
 {
-    return gaussian_u8_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
+    return blur_ch_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
 }
 
 // float32 images of 1, 3 or 4 channels
 int blur_gaussian_f32_batch_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, double sigma,
                                 const blur_opts* opts)
 {
-    return blur_f32_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts);
+    return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts);
 }
 
 int blur_gaussian_f32_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
 {
-    return blur_f32_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigma, opts);
+    return blur_ch_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigma, opts);
 }
 
 int blur_gaussian_f32_host(blur_ctx* ctx, const float* src, float* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
 {
-    if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
-    if (!src || !dst || rows <= 0 || cols <= 0 || !(sigma > 0)) return fail(ctx, BLUR_ERR_INVALID, "null image or non-positive size");
-    {
-        const Sizing sz = pffft_sizing(rows, cols, sigma);
-        if (sz.pad > rows - 1 || sz.pad > cols - 1)
-            return fail(ctx, BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1: reflect-101 would read outside the image (README.md:33-38)");
-    }
-    if (!ctx) return BLUR_ERR_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = static_cast<size_t>(rows) * cols * channels * sizeof(float), half = (bytes + 255) & ~static_cast<size_t>(255);
-    void* dv = nullptr;
-    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;      // source and destination: no in-place copy
-    char* d = static_cast<char*>(dv);
-    int rc = BLUR_OK;
-    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) rc = blur_f32_batch_impl(ctx, reinterpret_cast<const float*>(d), reinterpret_cast<float*>(d + half), 1, rows, cols, channels, sigma, opts);
-    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
-    return rc;
-}
-
-static int gaussian_f32_multi(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels, double sigma,
-                              const blur_opts* opts, int location)
-{
-    if (!m) return BLUR_ERR_INVALID;
-    if (channels != 1 && channels != 3 && channels != 4) { m->err = "channels must be 1, 3 or 4"; return BLUR_ERR_INVALID; }
-    if (!src || !dst || nframes < 0) { m->err = "null frame pointer or negative frame count"; return BLUR_ERR_INVALID; }
-    if (nframes == 0) return BLUR_OK;
-    if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
-    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels * sizeof(float) : 0;
-    return blur_multi_run(m, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nframes, fb, location,
-                          [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) {
-                              return blur_f32_batch_impl(c, reinterpret_cast<const float*>(in), reinterpret_cast<float*>(out), n, rows, cols, channels, sigma, opts);
-                          });
+    return blur_ch_host(ctx, src, dst, rows, cols, channels, sigma, opts);
 }
 
 int blur_gaussian_f32_batch_multi_dev(blur_multi* m, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, double sigma,
                                       const blur_opts* opts)
 {
-    return gaussian_f32_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, 1);
+    return blur_ch_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, 1);
 }
 
 int blur_gaussian_f32_batch_multi_host(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels, double sigma,
                                        const blur_opts* opts)
 {
-    return gaussian_f32_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
+    return blur_ch_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
 }
 
 int blur_convolve_lines_c32_dev(blur_ctx* ctx, const float* d_in, float* d_out, int nlines, int n, const float* multipliers)

@@ -397,40 +397,17 @@ template <int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const float* 
                                                    bool quirk, const float* strips)
 {
     using C = FfCfg<NKB>;
-    const int chunks = (g.cols + kFxChunk - 1) / kFxChunk;
-    const long long nstripes = static_cast<long long>(chunks) * g.nframes * CH;       // (strip of columns, channel)
-    if (nstripes <= 0) return hipSuccess;
-    // segments per strip as in fw_launch_u8: the shortest makespan = rounds x (tiles per segment + NT of run-in).  (The segments
-    // change no result: every output tile sums its products in the same order in any segment.)
-    int nseg = 1, tps = g.ntiles;
-    {
-        long long best = -1;
-        for (int n = 1; n <= g.ntiles; ++n) {
-            const int t = (g.ntiles + n - 1) / n, ns = (g.ntiles + t - 1) / t;
-            const long long rounds = (nstripes * ns + num_cus - 1) / num_cus, span = rounds * (t + C::NT);
-            if (best < 0 || span < best) { best = span; nseg = ns; tps = t; }
-        }
-    }
-    const long long ntasks = nstripes * nseg;
-    if (g.nxcd < 1) g.nxcd = 1;
-    const int per_xcd = static_cast<int>((ntasks + g.nxcd - 1) / g.nxcd);
-    const dim3 grid(static_cast<unsigned>(g.nxcd * per_xcd));
+    const FxLaunch l = fx_plan_launch(g, CH, C::NT, num_cus);
+    if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
-    int dev;
-    if (fx_attr_needed(attr_done, dev)) {
-        const void* kernels[2] = { reinterpret_cast<const void*>(ff_blur_f32<NKB, true, CH>), reinterpret_cast<const void*>(ff_blur_f32<NKB, false, CH>) };
-        for (const void* k : kernels) {
-            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-            if (e != hipSuccess) return e;
-        }
-        fx_attr_mark(attr_done, dev);
-    }
+    const hipError_t e = fx_set_lds(attr_done, C::LDS, ff_blur_f32<NKB, true, CH>, ff_blur_f32<NKB, false, CH>);
+    if (e != hipSuccess) return e;
     if (quirk)
-        hipLaunchKernelGGL((ff_blur_f32<NKB, true, CH>), grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, chunks, tps, nseg,
-                           static_cast<int>(ntasks), qk, strips);
+        hipLaunchKernelGGL((ff_blur_f32<NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
+                           l.nseg, static_cast<int>(l.ntasks), qk, strips);
     else
-        hipLaunchKernelGGL((ff_blur_f32<NKB, false, CH>), grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, chunks, tps, nseg,
-                           static_cast<int>(ntasks), qk, strips);
+        hipLaunchKernelGGL((ff_blur_f32<NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
+                           l.nseg, static_cast<int>(l.ntasks), qk, strips);
     return hipGetLastError();
 }
 

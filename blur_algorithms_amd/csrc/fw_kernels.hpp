@@ -382,42 +382,17 @@ template <int NKB> hipError_t fw_launch_u8(hipStream_t st, const uint8_t* src, u
 {
     using C = FwCfg<NKB>;
     if (vdump || stamps) return hipErrorNotSupported;            // the row-pass dump and the phase stamps are builds of fx_blur_u8 only
-    const int chunks = (g.cols + kFxChunk - 1) / kFxChunk;
-    const long long nstripes = static_cast<long long>(chunks) * g.nframes * 3;      // (strip of columns, channel)
-    if (nstripes <= 0) return hipSuccess;
-    // segments per strip as in fx_launch_u8: the shortest makespan = rounds x (tiles per segment + NT of run-in)
-    int nseg = 1, tps = g.ntiles;
-    {
-        // (any number of tiles per segment: the unrolled rotation of the accumulator tiles is relative to the segment's first step.
-        // Rounds 3-4 rounded it up to a multiple of NT for no reason the kernel has: 1080p, 8 frames, was cut in segments of 20 and 14
-        // tiles -- 25 steps -- instead of 17 and 17 -- 22 steps)
-        long long best = -1;
-        for (int n = 1; n <= g.ntiles; ++n) {
-            const int t = (g.ntiles + n - 1) / n, ns = (g.ntiles + t - 1) / t;
-            const long long rounds = (nstripes * ns + num_cus - 1) / num_cus, span = rounds * (t + C::NT);
-            if (best < 0 || span < best) { best = span; nseg = ns; tps = t; }
-        }
-    }
-    const long long ntasks = nstripes * nseg;
-    if (g.nxcd < 1) g.nxcd = 1;
-    const int per_xcd = static_cast<int>((ntasks + g.nxcd - 1) / g.nxcd);
-    const dim3 grid(static_cast<unsigned>(g.nxcd * per_xcd));
+    const FxLaunch l = fx_plan_launch(g, 3, C::NT, num_cus);
+    if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
-    int dev;
-    if (fx_attr_needed(attr_done, dev)) {
-        const void* kernels[2] = { reinterpret_cast<const void*>(fw_blur_u8<NKB, true>), reinterpret_cast<const void*>(fw_blur_u8<NKB, false>) };
-        for (const void* k : kernels) {
-            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-            if (e != hipSuccess) return e;
-        }
-        fx_attr_mark(attr_done, dev);
-    }
+    const hipError_t e = fx_set_lds(attr_done, C::LDS, fw_blur_u8<NKB, true>, fw_blur_u8<NKB, false>);
+    if (e != hipSuccess) return e;
     if (qk)
-        hipLaunchKernelGGL((fw_blur_u8<NKB, true>), grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, chunks, tps, nseg,
-                           static_cast<int>(ntasks), *qk, strips);
+        hipLaunchKernelGGL((fw_blur_u8<NKB, true>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
+                           l.nseg, static_cast<int>(l.ntasks), *qk, strips);
     else
-        hipLaunchKernelGGL((fw_blur_u8<NKB, false>), grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, chunks, tps, nseg,
-                           static_cast<int>(ntasks), FxQuirk{}, strips);
+        hipLaunchKernelGGL((fw_blur_u8<NKB, false>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
+                           l.nseg, static_cast<int>(l.ntasks), FxQuirk{}, strips);
     return hipGetLastError();
 }
 

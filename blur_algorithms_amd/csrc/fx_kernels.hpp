@@ -1069,17 +1069,55 @@ __global__ __launch_bounds__(256) void fx_prepass(const uint8_t* __restrict__ sr
 #endif  // BLUR_FX_QUIRK_KERNELS
 
 // ---- launcher ----------------------------------------------------------------------------------------------------------
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE: remember per device which kernel sets have it (blur_multi_* drives
-// several devices from one process; a process-wide flag would raise the limit on the first device only).  Devices past 63: every call.
-inline bool fx_attr_needed(std::atomic<unsigned long long>& done, int& dev)
+// The task grid shared by the fused launchers (fx_launch_u8, fw_launch_u8, fc_launch_ch, ff_launch_ch; bench.py:
+// fused_launch_shape models it).  One task is a segment of a stripe: a strip of kFxChunk columns of one frame and, for the kernels
+// that take one channel per task, one of its nch channels.  ntasks == 0: nothing to launch.
+struct FxLaunch {
+    int chunks = 0, nseg = 1, tps = 0;
+    long long ntasks = 0;
+    dim3 grid;
+};
+inline FxLaunch fx_plan_launch(FxGeom& g, int nch, int nt, int num_cus)
 {
-    dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-    return ((done.load(std::memory_order_acquire) >> dev) & 1ull) == 0;
+    FxLaunch l;
+    l.chunks = (g.cols + kFxChunk - 1) / kFxChunk;
+    const long long nstripes = static_cast<long long>(l.chunks) * g.nframes * nch;
+    if (nstripes <= 0) return l;
+    // Segments per strip of columns: a segment of t tiles takes t + NT steps (NT of run-in), and the chip runs num_cus tasks at a
+    // time; take the number of segments with the shortest makespan = rounds x steps per task (one segment unless the strips
+    // are too few to fill the chip: 240 strips of a 4K batch of 8 stay whole, a single 4K frame is cut in 8).  (The segments
+    // change no result: every output tile sums its products in the same order in any segment.)
+    // (any number of tiles per segment: the unrolled rotation of the accumulator tiles is relative to the segment's first step.
+    // Rounds 3-4 rounded it up to a multiple of NT for no reason the kernel has: 1080p, 8 frames, was cut in segments of 20 and 14
+    // tiles -- 25 steps -- instead of 17 and 17 -- 22 steps)
+    l.tps = g.ntiles;
+    long long best = -1;
+    for (int n = 1; n <= g.ntiles; ++n) {
+        const int t = (g.ntiles + n - 1) / n, ns = (g.ntiles + t - 1) / t;
+        const long long rounds = (nstripes * ns + num_cus - 1) / num_cus, span = rounds * (t + nt);
+        if (best < 0 || span < best) { best = span; l.nseg = ns; l.tps = t; }
+    }
+    l.ntasks = nstripes * l.nseg;
+    if (g.nxcd < 1) g.nxcd = 1;
+    const int per_xcd = static_cast<int>((l.ntasks + g.nxcd - 1) / g.nxcd);
+    l.grid = dim3(static_cast<unsigned>(g.nxcd * per_xcd));
+    return l;
 }
-inline void fx_attr_mark(std::atomic<unsigned long long>& done, int dev)
+
+// Raises the dynamic LDS limit of a launcher's kernels to `lds`.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE:
+// `done` (one per launcher instantiation) remembers per device which kernel sets have it (blur_multi_* drives several devices from
+// one process; a process-wide flag would raise the limit on the first device only).  Devices past 63: every call.
+template <class... K> hipError_t fx_set_lds(std::atomic<unsigned long long>& done, int lds, K... kernels)
 {
-    if (dev >= 0 && dev < 64) done.fetch_or(1ull << dev, std::memory_order_release);
+    int dev = -1;
+    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
+    if (known && ((done.load(std::memory_order_acquire) >> dev) & 1ull)) return hipSuccess;
+    for (const void* k : { reinterpret_cast<const void*>(kernels)... }) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+    }
+    if (known) done.fetch_or(1ull << dev, std::memory_order_release);
+    return hipSuccess;
 }
 
 struct FxEntry {
@@ -1093,43 +1131,15 @@ template <int NKB> hipError_t fx_launch_u8(hipStream_t st, const uint8_t* src, u
                                            const uint8_t* strips, float* vdump, unsigned long long* stamps)
 {
     using C = FxCfg<NKB>;
-    const int chunks = (g.cols + kFxChunk - 1) / kFxChunk;
-    const long long nstripes = static_cast<long long>(chunks) * g.nframes;
-    if (nstripes <= 0) return hipSuccess;
-    // Segments per strip of columns: a segment of t tiles takes t + NT steps (NT of run-in), and the chip runs num_cus tasks at a
-    // time; take the number of segments with the shortest makespan = rounds x steps per task (one segment unless the strips
-    // are too few to fill the chip: 240 strips of a 4K batch of 8 stay whole, a single 4K frame is cut in 8)
-    int nseg = 1, tps = g.ntiles;
-    {
-        // (any number of tiles per segment: the unrolled rotation of the accumulator tiles is relative to the segment's first step.
-        // Rounds 3-4 rounded it up to a multiple of NT for no reason the kernel has: 1080p, 8 frames, was cut in segments of 20 and 14
-        // tiles -- 25 steps -- instead of 17 and 17 -- 22 steps)
-        long long best = -1;
-        for (int n = 1; n <= g.ntiles; ++n) {
-            const int t = (g.ntiles + n - 1) / n, ns = (g.ntiles + t - 1) / t;
-            const long long rounds = (nstripes * ns + num_cus - 1) / num_cus, span = rounds * (t + C::NT);
-            if (best < 0 || span < best) { best = span; nseg = ns; tps = t; }
-        }
-    }
-    const long long ntasks = nstripes * nseg;
-    if (g.nxcd < 1) g.nxcd = 1;
-    const int per_xcd = static_cast<int>((ntasks + g.nxcd - 1) / g.nxcd);
-    const dim3 grid(static_cast<unsigned>(g.nxcd * per_xcd));
+    const FxLaunch l = fx_plan_launch(g, 1, C::NT, num_cus);
+    if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
-    int dev;
-    if (fx_attr_needed(attr_done, dev)) {
-        const void* kernels[6] = { reinterpret_cast<const void*>(fx_blur_u8<NKB, true, false>), reinterpret_cast<const void*>(fx_blur_u8<NKB, false, false>),
-                                   reinterpret_cast<const void*>(fx_blur_u8<NKB, true, true>), reinterpret_cast<const void*>(fx_blur_u8<NKB, false, true>),
-                                   reinterpret_cast<const void*>(fx_blur_u8<NKB, true, false, true>), reinterpret_cast<const void*>(fx_blur_u8<NKB, false, false, true>) };
-        for (const void* k : kernels) {
-            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-            if (e != hipSuccess) return e;
-        }
-        fx_attr_mark(attr_done, dev);
-    }
+    const hipError_t e = fx_set_lds(attr_done, C::LDS, fx_blur_u8<NKB, true, false>, fx_blur_u8<NKB, false, false>, fx_blur_u8<NKB, true, true>,
+                                    fx_blur_u8<NKB, false, true>, fx_blur_u8<NKB, true, false, true>, fx_blur_u8<NKB, false, false, true>);
+    if (e != hipSuccess) return e;
 #define FX_LAUNCH(Q_, D_, R_)                                                                                                                              \
-    hipLaunchKernelGGL((fx_blur_u8<NKB, Q_, D_, R_>), grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, chunks, tps, nseg, \
-                       static_cast<int>(ntasks), qk ? *qk : FxQuirk{}, strips, vdump ? vdump : reinterpret_cast<float*>(stamps))
+    hipLaunchKernelGGL((fx_blur_u8<NKB, Q_, D_, R_>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps, \
+                       l.nseg, static_cast<int>(l.ntasks), qk ? *qk : FxQuirk{}, strips, vdump ? vdump : reinterpret_cast<float*>(stamps))
     const bool ragged = (g.cols & 3) != 0;
     if (vdump) {
         if (ragged) return hipErrorNotSupported;                 // (the row-pass dump is a test instantiation: whole quads only)

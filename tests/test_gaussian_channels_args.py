@@ -60,6 +60,7 @@ def test_sigma_too_large_for_the_shape(channels):
     assert B.pffft_sizing(rows, cols, big)["pad"] > rows - 1
     assert L.blur_gaussian_u8_batch_dev(None, P, P, 1, rows, cols, channels, big, C.byref(o)) == UNSUPPORTED
     assert L.blur_gaussian_u8_dev(None, P, P, rows, cols, channels, big, C.byref(o)) == UNSUPPORTED
+    assert L.blur_gaussian_u8_host(None, P, P, rows, cols, channels, big, C.byref(o)) == UNSUPPORTED
     small = 2.0
     assert B.pffft_sizing(rows, cols, small)["pad"] <= rows - 1
     assert L.blur_gaussian_u8_batch_dev(None, P, P, 1, rows, cols, channels, small, C.byref(o)) == INVALID
@@ -70,9 +71,36 @@ def test_python_shapes():
     assert _gauss_frames_shape((5, 7)) == (1, 5, 7, 1)
     assert _gauss_frames_shape((5, 7, 4)) == (1, 5, 7, 4)
     assert _gauss_frames_shape((3, 5, 7, 1)) == (3, 5, 7, 1)
-    for bad in ((5, 7, 2), (5,), (2, 5, 7, 5), (1, 2, 3, 4, 5)):
+    for bad in ((5, 7, 2), (5,), (2, 5, 7, 5), (1, 2, 3, 4, 5), (0, 5), (4, 0, 1), (2, 4, 0, 3)):
         with pytest.raises(ValueError):
             _gauss_frames_shape(bad)
+
+
+def test_multi_refuses_a_mismatched_out_before_the_library():
+    """BlurMulti.gaussian on the numpy path: an `out` of another shape, dtype or layout is refused before the library is called (it
+    would be written past its end)"""
+    import numpy as np
+    from blur_algorithms_amd import api
+
+    class NoLib:
+        def blur_opts_default(self, o):
+            pass
+
+        def __getattr__(self, name):
+            def called(*args):
+                raise AssertionError("the library was called: %s" % name)
+            return called
+
+    m = object.__new__(api.BlurMulti)
+    m._lib = NoLib()
+    m._h = None
+    m.devices = [0]
+    frames = np.zeros((2, 8, 8, 4), np.uint8)
+    for bad in (np.zeros((1, 8, 8, 4), np.uint8), np.zeros((2, 8, 8, 4), np.float32), np.zeros((2, 8, 8, 4), np.uint8)[:, ::-1], [0] * 512):
+        with pytest.raises(ValueError):
+            api.BlurMulti.gaussian(m, frames, 2.0, out=bad)
+    with pytest.raises(ValueError):
+        api.BlurMulti.gaussian_f32(m, frames.astype(np.float32), 2.0, out=np.zeros((2, 8, 8, 4), np.uint8))
 
 
 # ---- host mirror of the staging geometry of fc_blur_u8 ----------------------------------------------------------------

@@ -89,6 +89,7 @@ def test_python_shapes_and_dtypes():
     assert api._gauss_f32_frames_shape((4, 5)) == (1, 4, 5, 1)
     assert api._gauss_f32_frames_shape((4, 5, 3)) == (1, 4, 5, 3)
     assert api._gauss_f32_frames_shape((2, 4, 5, 4)) == (2, 4, 5, 4)
+    assert api._gauss_f32_frames_shape is api._gauss_frames_shape          # one helper for both dtypes
     # dtype and layout are refused before the context is used
     ctx = object.__new__(api.BlurContext)
     ctx._lib = lib()

@@ -52,7 +52,7 @@ def test_multi_handle_on_the_c4_shard_shape(ctx):
 def test_two_contexts_two_host_threads_fused_kernel_concurrently():
     """two blur_ctx on device 0, each with its own stream, driven from two host threads at the same time (ctypes releases the GIL
     during a call): the closest a one-GPU box gets to blur_multi_* on distinct devices.  Every context sets the kernels' LDS
-    attribute for its device itself (fx_attr_needed: per device, not per process) and the two launches share the chip; each thread's
+    attribute for its device itself (fx_set_lds: per device, not per process) and the two launches share the chip; each thread's
     bytes equal the single-context result, over several rounds and three kernel widths"""
     import threading
     import torch
