@@ -1702,7 +1702,6 @@ static int run_colpass_u8c3(blur_ctx* ctx, const float* planes, uint8_t* dst, in
 // 1- and 4-channel u8 images (blur_gaussian_u8_*) and float32 images of 1, 3 or 4 channels (blur_gaussian_f32_*): every channel
 // blurred on its own as pffft_() blurs one of its planes (u8 with the + 0.5f truncation, float32 without)
 // ======================================================================================
-#include "fc_registry.hpp"
 #include "ff_registry.hpp"
 
 static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
@@ -1719,7 +1718,7 @@ static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
     return BLUR_OK;
 }
 
-// the fused kernel for CH = 1, 4 (fc_kernels.hpp): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
+// the fused kernel for CH = 1, 4 (fw_kernels.hpp): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
 // Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).
 static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
 {

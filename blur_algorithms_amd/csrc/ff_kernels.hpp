@@ -1,7 +1,7 @@
 // ff_kernels.hpp -- the fused matrix-core kernel for float32 images of 1, 3 or 4 channels, every window class (NKB = 3 .. 23
 // blocks of 16 positions: pad <= 168).
 //
-// The structure is fc_kernels.hpp's: a workgroup handles ONE channel of a strip of 128 pixel columns (channel fastest in the task
+// The structure is fw_kernels.hpp's: a workgroup handles ONE channel of a strip of 128 pixel columns (channel fastest in the task
 // list), stages its window through LDS, runs the row pass, the hand-off inside the registers, the sliding column-pass accumulators
 // and the emission.  What a float input changes:
 //   * range: each frame gets a power-of-two scale s = 2^e (ff_scale_exp) with max|x| s B <= 2^14, B = 1 + |dr| (cols + 2 pad) the

@@ -1,16 +1,17 @@
-// ff_registry.hpp -- the window sizes (NKB blocks of 16 positions) the fused kernels for float32 images are instantiated for, one
-// translation unit each (ff_conv_<NKB>.hip): the same classes as fc_registry.hpp.  A kernel serves every pad <= 8 (NKB - 2).
+// ff_registry.hpp -- the fused kernels for float32 images, one translation unit per window class of fx_registry.hpp
+// (ff_conv_<NKB>.hip).  A kernel serves every pad <= 8 (NKB - 2).
 #pragma once
 #include "ff_kernels.hpp"
+#include "fx_registry.hpp"
 namespace blur_amd {
 #define BLUR_FF_DECL(NKB_) const FfEntry* ff_entry_##NKB_();
-BLUR_FF_DECL(3) BLUR_FF_DECL(5) BLUR_FF_DECL(7) BLUR_FF_DECL(9) BLUR_FF_DECL(11)
-BLUR_FF_DECL(13) BLUR_FF_DECL(15) BLUR_FF_DECL(17) BLUR_FF_DECL(19) BLUR_FF_DECL(21) BLUR_FF_DECL(23)
+BLUR_FX_CLASSES(BLUR_FF_DECL)
 #undef BLUR_FF_DECL
 inline const FfEntry* find_ff_entry(int nkb)
 {
-    static const FfEntry* const list[] = { ff_entry_3(), ff_entry_5(), ff_entry_7(), ff_entry_9(), ff_entry_11(),
-                                           ff_entry_13(), ff_entry_15(), ff_entry_17(), ff_entry_19(), ff_entry_21(), ff_entry_23() };
+#define BLUR_FF_ITEM(NKB_) ff_entry_##NKB_(),
+    static const FfEntry* const list[] = { BLUR_FX_CLASSES(BLUR_FF_ITEM) };
+#undef BLUR_FF_ITEM
     for (const FfEntry* e : list)
         if (e->nkb == nkb) return e;
     return nullptr;

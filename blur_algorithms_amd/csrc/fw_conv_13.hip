@@ -1,3 +1,5 @@
-// fused matrix-core engine for wide windows, 13 window blocks of 16 positions: pad 73..88 (2 pad + 1 taps); one channel per workgroup
+// fused matrix-core kernel with one channel per workgroup, 13 window blocks of 16 positions (pad <= 88): 1 and 4 channels, and
+// 3 channels for pad 73 .. 88
 #include "fw_kernels.hpp"
 BLUR_FW(13)
+BLUR_FW_C3(13)

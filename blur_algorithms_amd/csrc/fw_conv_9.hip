@@ -1,0 +1,3 @@
+// fused matrix-core kernel with one channel per workgroup, 9 window blocks of 16 positions (pad <= 56): 1 and 4 channels
+#include "fw_kernels.hpp"
+BLUR_FW(9)

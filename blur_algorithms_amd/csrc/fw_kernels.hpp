@@ -1,18 +1,30 @@
-// fw_kernels.hpp -- the fused matrix-core kernel for WIDE windows (13 .. 23 blocks of 16 positions: kernel half widths 73 .. 168).
+// fw_kernels.hpp -- the fused matrix-core kernel that gives a workgroup ONE channel of its strip: u8 images of CH = 1, 3 or 4
+// channels (grayscale, BGR, BGRA / RGBA).  CH = 1 and 4 are instantiated for every window class (NKB = 3 .. 23 blocks of 16
+// positions: pad <= 168), CH = 3 for the WIDE windows only (NKB = 13 .. 23: pad 73 .. 168; narrower BGR windows run on fx_blur_u8).
 //
 // fx_kernels.hpp keeps (NKB - 1) / 2 column-pass accumulator tiles per channel and a wave carries all three channels: 240 AGPRs at
 // NKB = 11 and no room beyond.  Here a workgroup handles ONE channel of its strip of 128 pixel columns -- the task list has the
-// channel as its fastest dimension, so the three channel tasks of a strip run at the same time on neighbouring CUs of one XCD and
+// channel as its fastest dimension, so the CH channel tasks of a strip run at the same time on neighbouring CUs of one XCD and
 // share the window's cache lines -- which leaves (NKB - 1) / 2 <= 11 tiles = 176 AGPRs.  Everything else is the structure of
 // fx_kernels.hpp: window of the next step staged through LDS (binary16 subnormals straight from the bytes), row pass
 // D[32 rows][32 pixels] = window x Toeplitz fragments, hand-off inside the registers (scale, quirk term, hi + lo split,
 // v_permlane32_swap), sliding column-pass accumulators, emission with + 0.5f truncation.  Differences:
 //   * the hi halves of the fragments live in registers (4 NKB of them), the lo halves in LDS (one ds_read_b128 per use);
-//   * the output bytes of one channel are every third byte of the image: single byte stores (the three channel tasks' stores meet
-//     in L2 before the lines go to memory);
 //   * one product per step instead of three, and it is long (5 NKB = 115 matrix instructions at NKB = 23): the vector work of a
-//     step (staging 15 groups, the hand-off, the emission) is handed out between the products in a few places instead of
-//     instruction by instruction.
+//     step (staging, the hand-off, the emission) is handed out between the products in a few places instead of instruction by
+//     instruction.
+// What the channel count CH selects, at compile time:
+//   * staging: a group of 4 pixels is 4 CH bytes: one dword (CH = 1: the bytes are the four values), three dwords (CH = 3: two
+//     v_perm_b32 with run-time selectors, the channel is the task's) or one dwordx4 (CH = 4: byte c of each dword);
+//   * the quirk's sums: CH = 3 reads fx_prepass's (struct FxQuirk: Srow in parts per batch, the column term by
+//     fx_quirk_cols_tile), CH = 1 and 4 those of fc_prepass below (struct FcQuirk: Srow complete, fc_quirk_cols_tile);
+//   * stores: CH = 1 transposes a finished tile's bytes inside lane quads (fx_quad_transpose) so that a lane owns 4 adjacent pixels
+//     of one row: one dword store per lane and row group.  CH = 3 and 4 store single bytes: the output bytes of one channel are
+//     every CH-th byte of the image (the channel tasks' stores meet in L2 before the lines go to memory);
+//   * narrow windows (CH = 1, 4 only): the vector work of a step goes out over the column pass's NKB triples (the hand-off in
+//     slots 0 .. 7, the emission in 1 .. 4, the staging from slot 5 on) and the stores over the row pass's first four blocks.
+//     Below NKB = 9 there are fewer slots than that: the loops run on past the products, max(NKB, 9) and max(NKB, 4) slots, the
+//     ones beyond NKB holding only vector work.
 #pragma once
 #include "fx_kernels.hpp"
 #include <type_traits>
@@ -29,11 +41,7 @@ template <int NKB> struct FwCfg {
     // FxCfg -- a masked commit is a branch in the middle of a slice of matrix instructions), so a row holds 32 PER positions; the
     // pitch is 4 mod 8 dwords (conflict-free ds_read_b128, and ds_write_b64 with the staging rows of a 16-lane group 4 apart)
     static constexpr int fw_pitch() { int dw = 16 * PER; while ((dw & 7) != 4) ++dw; return 2 * dw; }
-#ifdef FW_MASKED_COMMITS      // (rounds 3-4 A/B: lane-masked commits, the row term by threads 0 .. 31 only, the window's own pitch)
-    static constexpr int PW = mx_row_pitch(NKB);
-#else
     static constexpr int PW = fw_pitch();
-#endif
     static constexpr int NT = (NKB - 1) / 2;                          // live accumulator tiles = steps per unrolled round
     static constexpr int BUF = 32 * PW * 2;                           // bytes of one window buffer (one channel)
     static constexpr int TLOFF = 2 * BUF;                             // lo halves of the fragments: [NKB][64 lanes] x 16 bytes
@@ -41,23 +49,96 @@ template <int NKB> struct FwCfg {
     static constexpr int LDS = QOFF + 2 * 2 * 32 * 4;
 };
 
-template <int NKB, bool QUIRK>
-__global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
-                                                     int chunks, int tps, int nseg, int ntasks, FxQuirk qk, const uint8_t* __restrict__ strips)
+// Whole-frame partial sums of the quirk for a 1- or 4-channel image (fc_prepass), read by fw_blur_u8<NKB, true, 1 / 4>:
+//   srow [frame][row][CH]             Srow(r, c) = sum_x wx(x) img[r][x][c]          (complete: the batches add with atomics)
+//   cpart[frame][band][cpitch]        sum over the band's rows of wy(r) img[r][x][c] at CH x + c
+//   zsum [frame][CH]                  Z(c) = sum_r wy(r) Srow(r, c)                  (complete, 64-bit)
+struct FcQuirk {
+    const int* srow;
+    const int* cpart;
+    const long long* zsum;
+    const float* taps;          // the 2 pad + 1 taps of the row pass, centre at pad
+    int nbands, cpitch;
+    float dr, dc;
+};
+
+// the quirk's sums the kernel reads: fx_prepass's for three channels, fc_prepass's for one and four
+template <int CH> using FwQuirk = std::conditional_t<CH == 3, FxQuirk, FcQuirk>;
+
+// dwords of a row per pre-pass thread: batches of 256 G dwords (G = 1, 2, 4); as many batches as the row needs
+inline int fc_groups_per_thread(int cols, int ch)
 {
+    const int dw = (cols * ch + 3) / 4;
+    return dw <= 256 ? 1 : (dw <= 512 ? 2 : 4);
+}
+
+// qc[xl] (xl = 0 .. 127) = the column term of pixel x0 + xl in channel c0, 0 right of the image (fx_quirk_cols_tile for a
+// CH-channel layout and one channel).  256 threads; `scratch` = LDS for (128 + 2 pad) + 2 pad + 1 doubles; ends with a barrier.
+template <int CH>
+__device__ __forceinline__ void fc_quirk_cols_tile(unsigned char* scratch, float* qc, const FcQuirk& q, int f, int x0, int c0, int cols, int pad, int tid)
+{
+    const int win = kFxChunk + 2 * pad, ntap = 2 * pad + 1;
+    double* cc = reinterpret_cast<double*>(scratch);
+    double* tp = cc + win;
+    const int* base = q.cpart + static_cast<size_t>(f) * q.nbands * q.cpitch + c0;
+    for (int p = tid; p < win; p += 256) {
+        const int* cp = base + CH * mx_refl(x0 - pad + p, cols);
+        int sum = 0;
+        int b = 0;
+        for (; b + 8 <= q.nbands; b += 8) {
+            int t[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) t[j] = cp[static_cast<size_t>(b + j) * q.cpitch];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sum += t[j];
+        }
+        for (; b < q.nbands; ++b) sum += cp[static_cast<size_t>(b) * q.cpitch];
+        cc[p] = static_cast<double>(sum);
+    }
+    for (int i = tid; i < ntap; i += 256) tp[i] = static_cast<double>(q.taps[i]);
+    __syncthreads();
+    const double sp = (pad & 1) ? -1.0 : 1.0, z = static_cast<double>(q.zsum[static_cast<size_t>(f) * CH + c0]);
+    if (tid < kFxChunk) {
+        const int x = x0 + tid;
+        float out = 0.f;
+        if (x < cols) {
+            const double* ccx = cc + tid;                                    // tap t = -pad sits here
+            double acc[4] = { 0, 0, 0, 0 };
+            int t = 0;
+            for (; t + 8 <= ntap; t += 8) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j & 3] = __builtin_fma(tp[t + j], ccx[t + j], acc[j & 3]);
+            }
+            for (; t < ntap; ++t) acc[t & 3] = __builtin_fma(tp[t], ccx[t], acc[t & 3]);
+            const double sx = ((x + pad) & 1) ? -1.0 : 1.0;
+            out = static_cast<float>(static_cast<double>(q.dc) * sp * (((acc[0] + acc[1]) + (acc[2] + acc[3])) + static_cast<double>(q.dr) * sx * z));
+        }
+        qc[tid] = out;
+    }
+    __syncthreads();
+}
+
+// One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
+template <int NKB, bool QUIRK, int CH>
+__global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
+                                                     int chunks, int tps, int nseg, int ntasks, FwQuirk<CH> qk, const uint8_t* __restrict__ strips)
+{
+    static_assert(CH == 1 || CH == 4 || (CH == 3 && NKB >= 13), "one or four channels; three for the wide windows only (narrower: fx_blur_u8)");
     using C = FwCfg<NKB>;
     constexpr int PADA = C::PADA, PW = C::PW, NT = C::NT, PER = C::PER;
-    constexpr int IPS = (PER + NKB - 6) / (NKB - 5);             // staging items per column-pass slot from slot 5 on
+    constexpr int RS = NKB > 4 ? NKB : 4;                         // row-pass slots: the stores of the previous tile need four
+    constexpr int CS = NKB > 9 ? NKB : 9;                         // column-pass slots: hand-off 0 .. 7, emission 1 .. 4, staging from 5
+    constexpr int IPS = (PER + CS - 6) / (CS - 5);                // staging items per column-pass slot from slot 5 on
     extern __shared__ __attribute__((aligned(16))) unsigned char fw_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = lane & 31, h = lane >> 5;
 
     const int nx = g.nxcd, xcd = blockIdx.x % nx, in_xcd = blockIdx.x / nx, per_xcd = (ntasks + nx - 1) / nx, task = xcd * per_xcd + in_xcd;
     if (in_xcd >= per_xcd || task >= ntasks) return;
-    const int c = task % 3, xc = (task / 3) % chunks, seg = (task / (3 * chunks)) % nseg, f = task / (3 * chunks * nseg);
+    const int c = task % CH, xc = (task / CH) % chunks, seg = (task / (CH * chunks)) % nseg, f = task / (CH * chunks * nseg);
     const int x0 = xc * kFxChunk;
     const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
-    const uint8_t* img = src + static_cast<size_t>(f) * g.rows * g.cols * 3;
-    uint8_t* out = dst + static_cast<size_t>(f) * g.rows * g.cols * 3;
+    const uint8_t* img = src + static_cast<size_t>(f) * g.rows * g.cols * CH;
+    uint8_t* out = dst + static_cast<size_t>(f) * g.rows * g.cols * CH;
 
     // fragments: hi halves in registers; of the lo halves the first TLR in registers too, the rest in LDS (the row pass reads a
     // window fragment per block already: with every lo half from LDS as well its two products would wait for the LDS pipe)
@@ -76,11 +157,16 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
 
     float cpos = 0.5f, cneg = 0.5f;
     if (QUIRK) {
-        // the column term of this chunk's pixels in the task's channel (fx_kernels.hpp: fx_quirk_cols_tile; the window buffers are
-        // not in use yet: tile and taps in buffer 0, the result in buffer 1)
-        static_assert(C::BUF >= 8 * (C::WIN + 2 * C::PADA + 1 + 6) + 4 * (3 * C::WIN + 4), "fx_quirk_cols_tile's scratch fits window buffer 0");
+        // the column term of this chunk's pixels in the task's channel (the window buffers are not in use yet: scratch in buffer 0,
+        // the result in buffer 1)
         float* qc = reinterpret_cast<float*>(fw_lds + C::BUF);
-        fx_quirk_cols_tile<1>(fw_lds, qc, qk, f, x0, c, g.cols, g.pad, tid);
+        if constexpr (CH == 3) {
+            static_assert(C::BUF >= 8 * (C::WIN + 2 * C::PADA + 1 + 6) + 4 * (3 * C::WIN + 4), "fx_quirk_cols_tile's scratch fits window buffer 0");
+            fx_quirk_cols_tile<1>(fw_lds, qc, qk, f, x0, c, g.cols, g.pad, tid);
+        } else {
+            static_assert(C::BUF >= 8 * (C::WIN + 2 * C::PADA + 1) && C::BUF >= 4 * kFxChunk, "fc_quirk_cols_tile's scratch and result fit the window buffers");
+            fc_quirk_cols_tile<CH>(fw_lds, qc, qk, f, x0, c, g.cols, g.pad, tid);
+        }
         const float v = qc[32 * wave + m];
         cpos = 0.5f + v;
         cneg = 0.5f - v;
@@ -95,104 +181,108 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
     for (int k = 0; k < NT; ++k) acc[k] = zero;
     mx_float16 arow = zero, tfin = zero;
     uint32_t hl[2][2][8];               // hand-off, two of them (the next step's is made while this step's is consumed): [hi, lo][packed row pairs], block b = entries 4 b .. 4 b + 3
-    uint32_t rr[4];                     // finished tile per row group: the channel's bytes of 4 rows of the lane's pixel column
+    uint32_t rr[4];                     // finished tile per row group: the channel's bytes of 4 rows of the lane's pixel column (CH = 1: transposed)
 
     const int s0 = tile0, s1 = tile1 + NT;
     // the window's source: the image, or (edge chunks) a strip with the mirrored pixels in place -- as in fx_kernels.hpp
     constexpr int NLEFT = fx_left_strips(PADA);                // two chunks at the left edge once the window is wider than a chunk either side
     const int sidx = xc < NLEFT ? xc : (xc >= chunks - g.nright ? NLEFT + xc - (chunks - g.nright) : -1);      // uniform
-    const uint32_t pitch = sidx >= 0 ? 3u * C::WIN : 3u * static_cast<uint32_t>(g.cols);
-    const uint8_t* wbase = sidx >= 0 ? strips + (static_cast<size_t>(f) * (NLEFT + g.nright) + sidx) * g.rows * (3 * C::WIN) : img + 3 * (x0 - PADA);
-    const uint32_t wbytes = sidx >= 0 ? static_cast<uint32_t>(g.rows) * 3u * C::WIN : (static_cast<uint32_t>(g.rows) * g.cols - static_cast<uint32_t>(x0 - PADA)) * 3u;
+    const uint32_t pitch = sidx >= 0 ? static_cast<uint32_t>(CH * C::WIN) : static_cast<uint32_t>(CH) * static_cast<uint32_t>(g.cols);
+    const uint8_t* wbase = sidx >= 0 ? strips + (static_cast<size_t>(f) * (NLEFT + g.nright) + sidx) * g.rows * (CH * C::WIN) : img + CH * (x0 - PADA);
+    const uint32_t wbytes = sidx >= 0 ? static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(CH * C::WIN)
+                                      : (static_cast<uint32_t>(g.rows) * g.cols - static_cast<uint32_t>(x0 - PADA)) * static_cast<uint32_t>(CH);
     const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(wbase), 0, wbytes, kMxRsrcWord3);
-#ifdef FW_STAGE_LINEAR
-    const int srow = tid >> 3, g0 = tid & 7;
-#else
     const int srow = 8 * (tid >> 6) + ((tid >> 4) & 3) + 4 * ((tid >> 3) & 1), g0 = tid & 7;      // (fx_kernels.hpp: the staging map)
-#endif
-    uint32_t raw[PER][3];
-    int qpart[kFxMaxBatches] = {};
-    // the window of step s: thread t moves the twelve-byte groups (t & 7) + 8 k of row t >> 3, all requested at once (consumed one
-    // matrix-heavy pass later).  (A mapping with 2 rows x 384 contiguous bytes per wave load instead of 8 x 96 changed nothing.)
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    uint32_t raw[PER][CH];
+    int qpart[CH == 3 ? kFxMaxBatches : 1] = {};      // the row term's Srow: CH = 3 in fx_prepass's parts per batch, CH = 1, 4 complete
+    // the window of step s: thread t moves the groups of 4 pixels g0 + 8 k of row srow, all requested at once (consumed one
+    // matrix-heavy pass later).  (CH = 3: a mapping with 2 rows x 384 contiguous bytes per wave load instead of 8 x 96 changed nothing.)
     auto issue_window = [&](int s) __attribute__((always_inline)) {
-#ifdef FW_ABL_NOLOAD
-        if (s > s0 + 1) return;
-#endif
         const int r = mx_refl(32 * s - PADA + srow, g.rows);
-        const uint32_t off = static_cast<uint32_t>(r) * pitch + 12u * g0;
-        typedef uint32_t u3 __attribute__((ext_vector_type(3)));
+        const uint32_t off = static_cast<uint32_t>(r) * pitch + static_cast<uint32_t>(4 * CH * g0);
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const bool in = (C::GPR % 8 == 0) || k < PER - 1 || g0 < C::GPR % 8;
-            const u3 t = __builtin_amdgcn_raw_buffer_load_b96(rimg, in ? off + 96u * k : off, 0, 0);
-            raw[k][0] = t[0]; raw[k][1] = t[1]; raw[k][2] = t[2];
+            // (CH = 3 spells the offset out in its load: through `o` the compiler schedules that kernel differently)
+            const uint32_t o = in ? off + static_cast<uint32_t>(32 * CH * k) : off;
+            if constexpr (CH == 1) {
+                raw[k][0] = __builtin_amdgcn_raw_buffer_load_b32(rimg, o, 0, 0);
+            } else if constexpr (CH == 3) {
+                typedef uint32_t u3 __attribute__((ext_vector_type(3)));
+                const u3 t = __builtin_amdgcn_raw_buffer_load_b96(rimg, in ? off + 32u * CH * k : off, 0, 0);
+                raw[k][0] = t[0]; raw[k][1] = t[1]; raw[k][2] = t[2];
+            } else {
+                const u4 t = __builtin_amdgcn_raw_buffer_load_b128(rimg, o, 0, 0);
+                raw[k][0] = t[0]; raw[k][1] = t[1]; raw[k][2] = t[2]; raw[k][3] = t[3];
+            }
         }
-#ifdef FW_MASKED_COMMITS
-        if (QUIRK && tid < 32)
-#else
-        if (QUIRK)                      // the row term of row re of V (= image row refl(re - PADA)): dr (-1)^pad Srow; every thread (row tid & 31:
-#endif
-        {                               // eight copies of each value) -- a test on tid would be a branch in the middle of a slice of matrix instructions
-            const int* sp = qk.srow_part + (static_cast<size_t>(f) * qk.nbatches * g.rows + mx_refl(min(32 * s + (tid & 31), qrows - 1) - PADA, g.rows)) * 3 + c;
+        if (QUIRK) {                    // the row term of row re of V (= image row refl(re - PADA)): dr (-1)^pad Srow; every thread (row tid & 31:
+                                        // eight copies of each value) -- a test on tid would be a branch in the middle of a slice of matrix instructions
+            if constexpr (CH == 3) {
+                const int* sp = qk.srow_part + (static_cast<size_t>(f) * qk.nbatches * g.rows + mx_refl(min(32 * s + (tid & 31), qrows - 1) - PADA, g.rows)) * 3 + c;
 #pragma unroll
-            for (int b = 0; b < kFxMaxBatches; ++b) qpart[b] = sp[static_cast<size_t>(min(b, qk.nbatches - 1)) * g.rows * 3];      // (fx_kernels.hpp: issue_chunk)
+                for (int b = 0; b < kFxMaxBatches; ++b) qpart[b] = sp[static_cast<size_t>(min(b, qk.nbatches - 1)) * g.rows * 3];      // (fx_kernels.hpp: issue_chunk)
+            } else {
+                qpart[0] = qk.srow[(static_cast<size_t>(f) * g.rows + mx_refl(min(32 * s + (tid & 31), qrows - 1) - PADA, g.rows)) * CH + c];
+            }
         }
     };
-    // channel c of group k -> binary16 subnormals -> LDS: two v_perm_b32 (run-time selectors: the channel is the task's) and one
-    // ds_write_b64.  Pixels (0, 1) of the group are bytes (c, 3 + c), pixels (2, 3) bytes (6 + c, 9 + c) of its three dwords.
-    const uint32_t selA = c == 0 ? 0x0c030c00u : (c == 1 ? 0x0c040c01u : 0x0c050c02u);      // operands (d1, d0)
-    const uint32_t selB = c == 0 ? 0x0c050c02u : (c == 1 ? 0x0c060c03u : 0x0c070c00u);      // operands (d2, d1) / c == 2: (d2, d2)
+    // channel c of group k -> binary16 subnormals -> LDS: two v_perm_b32 and one ds_write_b64.  CH = 3: pixels (0, 1) of the group
+    // are bytes (c, 3 + c), pixels (2, 3) bytes (6 + c, 9 + c) of its three dwords; CH = 4: byte c of each dword
+    const uint32_t selA = CH == 3 ? (c == 0 ? 0x0c030c00u : (c == 1 ? 0x0c040c01u : 0x0c050c02u))                 // operands (d1, d0)
+                                  : 0x0c000c00u | (static_cast<uint32_t>(4 + c) << 16) | static_cast<uint32_t>(c);  // CH = 4: (d1, d0), (d3, d2)
+    const uint32_t selB = c == 0 ? 0x0c050c02u : (c == 1 ? 0x0c060c03u : 0x0c070c00u);                             // CH = 3: (d2, d1) / c == 2: (d2, d2)
     auto commit_item = [&](int buf, int k) __attribute__((always_inline)) {
-#ifdef FW_ABL_NOCOMMIT
-        if (buf >= 0) return;
-#endif
         if (k >= PER) return;
-#ifdef FW_MASKED_COMMITS
-        if ((C::GPR % 8 == 0) || k < PER - 1 || g0 < C::GPR % 8)
-#endif
-        {   // (groups past the window's GPR of the last k hold whatever their clamped load returned: they land in the row's padding)
-            _Float16* base = reinterpret_cast<_Float16*>(fw_lds + buf * C::BUF) + srow * PW + 4 * g0;
-            uint2 wd;
+        // (groups past the window's GPR of the last k hold whatever their clamped load returned: they land in the row's padding)
+        _Float16* base = reinterpret_cast<_Float16*>(fw_lds + buf * C::BUF) + srow * PW + 4 * g0;
+        uint2 wd;
+        if constexpr (CH == 1) {
+            wd.x = __builtin_amdgcn_perm(0u, raw[k][0], 0x0c010c00u);
+            wd.y = __builtin_amdgcn_perm(0u, raw[k][0], 0x0c030c02u);
+        } else if constexpr (CH == 3) {
             wd.x = __builtin_amdgcn_perm(raw[k][1], raw[k][0], selA);
             wd.y = __builtin_amdgcn_perm(raw[k][2], c == 2 ? raw[k][2] : raw[k][1], selB);
-            *reinterpret_cast<uint2*>(base + 32 * k) = wd;
+        } else {
+            wd.x = __builtin_amdgcn_perm(raw[k][1], raw[k][0], selA);
+            wd.y = __builtin_amdgcn_perm(raw[k][3], raw[k][2], selA);
         }
+        *reinterpret_cast<uint2*>(base + 32 * k) = wd;
     };
     auto commit_q = [&](int buf) __attribute__((always_inline)) {
-#ifdef FW_MASKED_COMMITS
-        if (QUIRK && tid < 32) {
-#else
         if (QUIRK) {                     // (every thread: the eight threads of a row store the same value to the same place)
-#endif
             int v = qpart[0];
+            if constexpr (CH == 3) {
 #pragma unroll
-            for (int b = 1; b < kFxMaxBatches; ++b) v += b < qk.nbatches ? qpart[b] : 0;
+                for (int b = 1; b < kFxMaxBatches; ++b) v += b < qk.nbatches ? qpart[b] : 0;
+            }
             const float qraw = static_cast<float>(qrs * v);
             float* qs = reinterpret_cast<float*>(fw_lds + C::QOFF) + buf * 64 + (tid & 31);
             qs[0] = qraw;            // the term enters as qrow (-1)^x: lanes of even x read this copy,
             qs[32] = -qraw;          // lanes of odd x this one
         }
     };
-    // R: the window in buffer `buf` -> arow; `beside(kb)` runs after the two products of window block kb
+    // R: the window in buffer `buf` -> arow; `beside(kb)` runs after the products of slot kb
     auto rowpass = [&](int buf, auto beside) __attribute__((always_inline)) {
         const _Float16* base = reinterpret_cast<const _Float16*>(fw_lds + buf * C::BUF) + m * PW + wave * 32 + 8 * h;
         mx_float16 a = zero;
         mx_half8 x[4], tq[3];                      // window fragments three blocks ahead, LDS-resident lo halves two blocks ahead
 #pragma unroll
-        for (int kb = 0; kb < 3; ++kb) x[kb] = *reinterpret_cast<const mx_half8*>(base + 16 * kb);
+        for (int kb = 0; kb < 3 && kb < NKB; ++kb) x[kb] = *reinterpret_cast<const mx_half8*>(base + 16 * kb);
         tq[0] = tlo(0);
         tq[1] = tlo(1);
 #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            if (kb + 3 < NKB) x[(kb + 3) & 3] = *reinterpret_cast<const mx_half8*>(base + 16 * (kb + 3));
-            if (kb + 2 < NKB) tq[(kb + 2) % 3] = tlo(kb + 2);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[kb & 3], th[kb], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[kb & 3], tq[kb % 3], a, 0, 0, 0);
-            asm volatile("" : "+a"(a));          // pins the two products between this block's fences
+        for (int kb = 0; kb < RS; ++kb) {
+            if (kb < NKB) {
+                if (kb + 3 < NKB) x[(kb + 3) & 3] = *reinterpret_cast<const mx_half8*>(base + 16 * (kb + 3));
+                if (kb + 2 < NKB) tq[(kb + 2) % 3] = tlo(kb + 2);
+                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[kb & 3], th[kb], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[kb & 3], tq[kb % 3], a, 0, 0, 0);
+                asm volatile("" : "+a"(a));          // pins the two products between this block's fences
+            }
             beside(kb);
-#ifndef FW_NOSB
-            __builtin_amdgcn_sched_barrier(0);   // the vector work handed out beside block kb stays beside block kb
-#endif
+            __builtin_amdgcn_sched_barrier(0);       // the vector work handed out beside slot kb stays beside slot kb
         }
         arow = a;
     };
@@ -235,9 +325,10 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
             fx_swap4(hp[4 * hf], hp[4 * hf + 2], hp[4 * hf + 1], hp[4 * hf + 3], lp[4 * hf], lp[4 * hf + 2], lp[4 * hf + 1], lp[4 * hf + 3]);
         }
     };
-    // E: four registers of the finished tile (rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column) -> bytes, kept in rr[gq].  No
-    // transposes: the lane keeps its COLUMN, so a store instruction covers 2 rows x 32 pixels (96-byte spans, two or three cache
-    // lines) instead of 8 rows x 8 quads.
+    // E: four registers of the finished tile (rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column) -> bytes, kept in rr[gq].  CH = 3,
+    // 4: no transposes, the lane keeps its COLUMN, so a store instruction covers 2 rows x 32 pixels.  CH = 1: transposed inside the
+    // lane quad: lane q of quad Q holds row 8 gq + 4 h + q, pixels 4 Q .. 4 Q + 3 of the wave's 32
+    const uint32_t sel1 = (lane & 1) ? 0x03070105u : 0x06020400u, sel2 = (lane & 2) ? 0x03020706u : 0x05040100u;
     auto emit_piece = [&](int gq) __attribute__((always_inline)) {
         float fv[4];
 #pragma unroll
@@ -248,13 +339,13 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
         // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
         const uint32_t b0 = static_cast<uint32_t>(static_cast<int>(fv[0])) & 0xffu, b1 = static_cast<uint32_t>(static_cast<int>(fv[1])) & 0xffu;
         const uint32_t b2 = static_cast<uint32_t>(static_cast<int>(fv[2])) & 0xffu, b3 = static_cast<uint32_t>(static_cast<int>(fv[3]));
-        rr[gq] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+        const uint32_t pk = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+        rr[gq] = CH == 1 ? fx_quad_transpose(pk, sel1, sel2) : pk;
     };
     // C: column pass of step slot qs from hl (fx_kernels.hpp: colpass): first the tile that FINISHES, last the tile that STARTS
     // `ri`: step ri of the segment's first NT (-1: a later step) -- the triples of tiles above the segment (a2 > ri) are left out
     // statically (fx_kernels.hpp: colpass)
     auto colpass = [&](int qs, int hb, int ri, auto beside) __attribute__((always_inline)) {
-        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
         mx_half8 v1[2], v2[2];
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
@@ -266,44 +357,58 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
         auto dof = [](int it) { return it == 0 ? NKB - 1 : (it >= NKB - 2 ? it - (NKB - 2) : it + 1); };
         mx_half8 tq[3];
         tq[0] = tlo(dof(0));
-        tq[1] = tlo(dof(1));
+        if (NKB > 1) tq[1] = tlo(dof(1));
 #pragma unroll
-        for (int it = 0; it < NKB; ++it) {
-            const int d = dof(it);
-            const int b = d & 1, a2 = d >> 1, slot = (qs - a2 + 2 * NT) % NT;
-            if (it + 2 < NKB) tq[(it + 2) % 3] = tlo(dof(it + 2));
-            if (ri < 0 || a2 <= ri) {
-                mx_float16 t = d == 0 ? zero : acc[slot];
-                t = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[d], v1[b], t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_32x32x16_f16(tq[it % 3], v1[b], t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[d], v2[b], t, 0, 0, 0);
-                asm volatile("" : "+a"(t));      // pins the three products between this triple's fences
-                if (it == 0) tfin = t; else acc[slot] = t;
+        for (int it = 0; it < CS; ++it) {
+            if (it < NKB) {
+                const int d = dof(it);
+                const int b = d & 1, a2 = d >> 1, slot = (qs - a2 + 2 * NT) % NT;
+                if (it + 2 < NKB) tq[(it + 2) % 3] = tlo(dof(it + 2));
+                if (ri < 0 || a2 <= ri) {
+                    mx_float16 t = d == 0 ? zero : acc[slot];
+                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[d], v1[b], t, 0, 0, 0);
+                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(tq[it % 3], v1[b], t, 0, 0, 0);
+                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[d], v2[b], t, 0, 0, 0);
+                    asm volatile("" : "+a"(t));      // pins the three products between this triple's fences
+                    if (it == 0) tfin = t; else acc[slot] = t;
+                }
             }
             beside(it);
-#ifndef FW_NOSB
             __builtin_amdgcn_sched_barrier(0);
-#endif
         }
     };
-    // F: the channel's bytes of the finished tile: byte c of every pixel (stride 3), rows 8 gq + 4 h + k of the lane's column.  Buffer
-    // stores: rows past the image, lanes right of it and tiles that do not exist get an offset outside the resource.
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows) * g.cols * 3u, kMxRsrcWord3);
-    const int xcol = x0 + 32 * wave + m;
-    const uint32_t lane_out = (static_cast<uint32_t>(4 * h) * g.cols + static_cast<uint32_t>(xcol)) * 3u + static_cast<uint32_t>(c);
-    const uint32_t rowstep = static_cast<uint32_t>(g.cols) * 3u;
+    // F: the finished tile's bytes.  Buffer stores: rows past the image, pixels right of it and tiles that do not exist get an
+    // offset outside the resource
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows) * g.cols * static_cast<uint32_t>(CH), kMxRsrcWord3);
+    const int xcol = x0 + 32 * wave + m;                                  // CH = 3, 4: the lane's pixel column
+    // CH = 3: byte c of the lane's pixel in row 4 h (the stores add the row group's offset to it; CH = 4 computes each offset whole.
+    // The two spellings keep each kernel's code as it was tuned: either one in the other kernel changes its registers and schedule)
+    const uint32_t lane_out = CH == 3 ? (static_cast<uint32_t>(4 * h) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c) : 0u;
+    const uint32_t rowstep = static_cast<uint32_t>(g.cols) * CH;
+    const int xq = x0 + 32 * wave + 4 * (m >> 2), q = m & 3;                // CH = 1: first pixel of the lane's quad, its row in the row group
+    const bool ragged = (g.cols & 3) != 0;                                // (uniform) CH = 1: the quad cut by the right edge leaves as bytes
+    const int qn = xq >= g.cols ? 0 : min(4, g.cols - xq);                // pixels of the lane's quad inside the image
     auto store_group = [&](int tile, bool valid, int gq) __attribute__((always_inline)) {
-        const int row0 = 32 * tile + 8 * gq + 4 * h;
-        const uint32_t base = lane_out + static_cast<uint32_t>(32 * tile + 8 * gq) * rowstep;
         const uint32_t v = rr[gq];
+        if constexpr (CH == 1) {
+            const int row = 32 * tile + 8 * gq + 4 * h + q;
+            const bool rok = valid && row < g.rows;
+            const uint32_t o = static_cast<uint32_t>(row) * rowstep + static_cast<uint32_t>(xq);
+            __builtin_amdgcn_raw_buffer_store_b32(v, rout, rok && qn == 4 ? o : 0xfffffff0u, 0, 0);
+            if (ragged) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#ifdef FW_ABL_NOSTORE
-            const bool ok = false && valid;
-#else
-            const bool ok = valid && xcol < g.cols && row0 + k < g.rows;
-#endif
-            __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(v >> (8 * k)), rout, ok ? base + k * rowstep : 0xfffffff0u, 0, 0);
+                for (int k = 0; k < 3; ++k)
+                    __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(v >> (8 * k)), rout, rok && qn < 4 && k < qn ? o + k : 0xfffffff0u, 0, 0);
+            }
+        } else {                                                          // byte c of every pixel, rows 8 gq + 4 h + k of the lane's column
+            const int row0 = 32 * tile + 8 * gq + 4 * h;
+            const uint32_t base = CH == 3 ? lane_out + static_cast<uint32_t>(32 * tile + 8 * gq) * rowstep
+                                          : (static_cast<uint32_t>(row0) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool ok = valid && xcol < g.cols && row0 + k < g.rows;
+                __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(v >> (8 * k)), rout, ok ? base + k * rowstep : 0xfffffff0u, 0, 0);
+            }
         }
     };
 
@@ -330,39 +435,31 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
     //               the tile this step finishes (slots 1 .. 4), window s + 2 group by group into the buffer window s left (from slot 5)
     // The step loop is unrolled NT times: the accumulator rotation is static, the window buffers alternate through a run-time offset.
     auto step = [&](int s, int qs, int ri) __attribute__((always_inline)) {
-        {
-            const int par = (s - s0) & 1;                      // window s: buffer par; window s + 1: the other one
-            const int ptile = s - 1 - NT;
-            const bool pvalid = ptile >= tile0 && s > s0;
-            issue_window(s + 2);
-            rowpass(par ^ 1, [&](int kb) __attribute__((always_inline)) {
-                if (kb < 4) store_group(ptile, pvalid, kb);
-            });
-            colpass(qs, 0, ri, [&](int it) __attribute__((always_inline)) {
-                if (it < 8) split_piece(par ^ 1, 1, it);
-                if (it >= 1 && it <= 4) emit_piece(it - 1);
-                if (it >= 5) {
+        const int par = (s - s0) & 1;                          // window s: buffer par; window s + 1: the other one
+        const int ptile = s - 1 - NT;
+        const bool pvalid = ptile >= tile0 && s > s0;
+        issue_window(s + 2);
+        rowpass(par ^ 1, [&](int kb) __attribute__((always_inline)) {
+            if (kb < 4) store_group(ptile, pvalid, kb);
+        });
+        colpass(qs, 0, ri, [&](int it) __attribute__((always_inline)) {
+            if (it < 8) split_piece(par ^ 1, 1, it);
+            if (it >= 1 && it <= 4) emit_piece(it - 1);
+            if (it >= 5) {
 #pragma unroll
-                    for (int i = 0; i < IPS; ++i) commit_item(par, IPS * (it - 5) + i);
-                }
-                if (it == NKB - 1) commit_q(par);
-            });
+                for (int i = 0; i < IPS; ++i) commit_item(par, IPS * (it - 5) + i);
+            }
+            if (it == CS - 1) commit_q(par);
+        });
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { hl[0][0][k] = hl[1][0][k]; hl[0][1][k] = hl[1][1][k]; }
-#ifndef FW_ABL_NOBARRIER
-            __syncthreads();                                   // window s + 2 complete, window s + 1 no longer read
-#endif
-        }
+        for (int k = 0; k < 8; ++k) { hl[0][0][k] = hl[1][0][k]; hl[0][1][k] = hl[1][1][k]; }
+        __syncthreads();                                       // window s + 2 complete, window s + 1 no longer read
     };
     // the first NT steps of a segment as their own copy of the body, without the column products of the tiles above the segment (about
     // half the column pass of these steps: NT = 11 for the widest window, where a single image's segments are 14 .. 20 steps long)
-#ifndef FW_NO_PEEL
 #pragma unroll
     for (int j = 0; j < NT; ++j) step(s0 + j, j, j);
     for (int sb = s0 + NT; sb < s1; sb += NT) {
-#else
-    for (int sb = s0; sb < s1; sb += NT) {
-#endif
 #pragma unroll
         for (int qs = 0; qs < NT; ++qs) {
             const int s = sb + qs;
@@ -377,32 +474,189 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
     }
 }
 
-template <int NKB> hipError_t fw_launch_u8(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk,
-                                           const uint8_t* strips, float* vdump, unsigned long long* stamps)
+template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FwQuirk<CH>* qk,
+                                               const uint8_t* strips)
 {
     using C = FwCfg<NKB>;
-    if (vdump || stamps) return hipErrorNotSupported;            // the row-pass dump and the phase stamps are builds of fx_blur_u8 only
-    const FxLaunch l = fx_plan_launch(g, 3, C::NT, num_cus);
+    const FxLaunch l = fx_plan_launch(g, CH, C::NT, num_cus);
     if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
-    const hipError_t e = fx_set_lds(attr_done, C::LDS, fw_blur_u8<NKB, true>, fw_blur_u8<NKB, false>);
+    const hipError_t e = fx_set_lds(attr_done, C::LDS, fw_blur_u8<NKB, true, CH>, fw_blur_u8<NKB, false, CH>);
     if (e != hipSuccess) return e;
     if (qk)
-        hipLaunchKernelGGL((fw_blur_u8<NKB, true>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
+        hipLaunchKernelGGL((fw_blur_u8<NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
                            l.nseg, static_cast<int>(l.ntasks), *qk, strips);
     else
-        hipLaunchKernelGGL((fw_blur_u8<NKB, false>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), FxQuirk{}, strips);
+        hipLaunchKernelGGL((fw_blur_u8<NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
+                           l.nseg, static_cast<int>(l.ntasks), FwQuirk<CH>{}, strips);
     return hipGetLastError();
 }
 
+// the three-channel entry (FxEntry; fx_registry.hpp: find_fx_entry) of the wide windows
+template <int NKB> hipError_t fw_launch_u8c3(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk,
+                                             const uint8_t* strips, float* vdump, unsigned long long* stamps)
+{
+    if (vdump || stamps) return hipErrorNotSupported;            // the row-pass dump and the phase stamps are builds of fx_blur_u8 only
+    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips);
+}
+
+struct FcEntry {
+    int nkb;
+    // ch: 1 or 4; qk: the quirk's sums (null: nyquist_quirk = 0)
+    hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk, const uint8_t* strips);
+};
+
+// the one- and four-channel entry (FcEntry; fx_registry.hpp: find_fc_entry) of every window class
+template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk,
+                                              const uint8_t* strips)
+{
+    if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips);
+    if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips);
+    return hipErrorInvalidValue;
+}
+
+// fw_conv_<NKB>.hip: BLUR_FW(NKB) for every window class, BLUR_FW_C3(NKB) as well for the wide ones
 #define BLUR_FW(NKB_)                                                                                       \
     namespace blur_amd {                                                                                    \
-    const FxEntry* fx_entry_##NKB_()                                                                        \
+    const FcEntry* fc_entry_##NKB_()                                                                        \
     {                                                                                                       \
-        static const FxEntry e = { NKB_, fw_launch_u8<NKB_> };                                              \
+        static const FcEntry e = { NKB_, fw_launch_u8c14<NKB_> };                                           \
         return &e;                                                                                          \
     }                                                                                                       \
     }
+#define BLUR_FW_C3(NKB_)                                                                                    \
+    namespace blur_amd {                                                                                    \
+    const FxEntry* fx_entry_##NKB_()                                                                        \
+    {                                                                                                       \
+        static const FxEntry e = { NKB_, fw_launch_u8c3<NKB_> };                                            \
+        return &e;                                                                                          \
+    }                                                                                                       \
+    }
+
+// ---- what runs before the 1- and 4-channel kernels (engine.hip) ------------------------------------------------------
+// strips[f][strip][row][CH (128 + 2 pada)]: the window of an edge chunk with the mirrored pixels in place (fx_edge_strips_body for
+// CH channels; the CH-channel kernel reads the whole window of an edge chunk from its strip).  A thread writes one dword.
+template <int CH>
+__device__ __forceinline__ void fc_edge_strips_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ strips, int rows, int cols, int pada, int chunks,
+                                                    int nright, int bx, int sidx, int f)
+{
+    const int win = kFxChunk + 2 * pada, dpr = CH * win / 4;            // dwords per strip row (win is a multiple of 4)
+    const int nleft = fx_left_strips(pada);
+    const int xc = sidx < nleft ? sidx : chunks - nright + sidx - nleft, x0 = kFxChunk * xc;
+    const int i = bx * 256 + threadIdx.x;
+    if (i >= rows * dpr) return;
+    const int r = i / dpr, d = i - r * dpr;
+    const uint8_t* line = src + (static_cast<size_t>(f) * rows + r) * cols * CH;
+    uint32_t o = 0;
+    const int X = x0 - pada + (CH == 1 ? 4 * d : d);                   // first pixel of the dword's window position
+    if (CH == 4) o = *reinterpret_cast<const uint32_t*>(line + 4 * mx_refl(X, cols));
+    else if (X >= 0 && X + 3 < cols) o = *reinterpret_cast<const uint32_t*>(line + X);
+    else {                                                             // a mirrored pixel (or past one reflection): byte by byte
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o |= static_cast<uint32_t>(line[mx_refl(X + k, cols)]) << (8 * k);
+    }
+    *reinterpret_cast<uint32_t*>(strips + ((static_cast<size_t>(f) * (nleft + nright) + sidx) * rows + r) * (CH * win) + 4 * d) = o;
+}
+
+// The quirk's sums (FcQuirk) for a CH-channel image: workgroup (band of band_rows rows, batch of 256 G dwords of a row, frame).
+// A thread owns G dwords of every row of the band: CH = 1 four pixels, CH = 4 one pixel's four channels.  Exact integers; srow and
+// zsum must be zero before the launch (they are completed with atomics).  sred[row][channel][lane]: lane l of every wave adds
+// into slot l (fx_altsums_body).
+constexpr int kFcSumRows = 32;
+template <int CH, int G>
+__device__ __forceinline__ void fc_altsums_body(const uint8_t* __restrict__ src, int* __restrict__ srow, int* __restrict__ cpart, long long* __restrict__ zsum,
+                                                int rows, int cols, int pad, int nbands, int cpitch, int band, int batch, int f, int (*sred)[CH][64], int band_rows)
+{
+    const int tid = threadIdx.x;
+    const uint32_t rowbytes = static_cast<uint32_t>(cols) * CH;
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src + static_cast<size_t>(f) * rows * rowbytes), 0,
+                                                                          static_cast<uint32_t>(rows) * rowbytes, kMxRsrcWord3);
+    const int ndw = static_cast<int>((rowbytes + 3) / 4), r0 = band * band_rows, r1 = min(r0 + band_rows, rows);
+    // a row that is no multiple of 4 bytes (cols * CH >= 4): its last dword is loaded `over` bytes early and shifted down, so that no
+    // load reaches past the row (the last row's would leave the buffer resource, which returns 0 for the WHOLE dword)
+    const int over = 4 * ndw - static_cast<int>(rowbytes);
+    int dj[G], wx[G][4], col[G][4], back[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        dj[j] = (batch * G + j) * 256 + tid;
+        back[j] = dj[j] == ndw - 1 ? over : 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int b = 4 * dj[j] + k, x = CH == 1 ? b : dj[j];          // pixel of byte k of the dword
+            wx[j][k] = dj[j] < ndw && b < static_cast<int>(rowbytes) ? mx_alt_weight(x, cols, pad) : 0;
+            col[j][k] = 0;
+        }
+    }
+    for (int rs = r0; rs < r1; rs += kFcSumRows) {
+        const int re = min(rs + kFcSumRows, r1);
+        for (int i = tid; i < kFcSumRows * CH * 64; i += 256) (&sred[0][0][0])[i] = 0;
+        __syncthreads();
+        constexpr int RB = G == 1 ? 8 : (G == 2 ? 4 : 2);                  // rows of loads in flight
+        for (int rb = rs; rb < re; rb += RB) {
+            uint32_t d[RB][G];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) {
+                const uint32_t roff = static_cast<uint32_t>(min(rb + i, re - 1)) * rowbytes;
+#pragma unroll
+                for (int j = 0; j < G; ++j)
+                    d[i][j] = __builtin_amdgcn_raw_buffer_load_b32(rimg, dj[j] < ndw ? roff + 4u * dj[j] - back[j] : 0xfffffff0u, 0, 0) >> (8 * back[j]);
+            }
+#pragma unroll
+            for (int i = 0; i < RB; ++i) {
+                const int r = rb + i;
+                if (r >= re) break;                                                // uniform
+                const int wy = mx_alt_weight(r, rows, pad);
+                int s[CH];
+#pragma unroll
+                for (int ch = 0; ch < CH; ++ch) s[ch] = 0;
+#pragma unroll
+                for (int j = 0; j < G; ++j)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int v = wx[j][k] != 0 ? static_cast<int>((d[i][j] >> (8 * k)) & 0xffu) : 0;      // (bytes of the next row: weight 0)
+                        s[CH == 1 ? 0 : k % CH] += wx[j][k] * v;
+                        col[j][k] += wy * v;
+                    }
+#pragma unroll
+                for (int ch = 0; ch < CH; ++ch) atomicAdd(&sred[r - rs][ch][tid & 63], s[ch]);
+            }
+        }
+        __syncthreads();
+        if (tid < (re - rs) * CH) {
+            const int rr = tid / CH, ch = tid - rr * CH;
+            const int* p64 = &sred[rr][ch][0];
+            int v = 0;
+#pragma unroll 8
+            for (int k = 0; k < 64; ++k) v += p64[(k + tid) & 63];
+            atomicAdd(&srow[(static_cast<size_t>(f) * rows + rs + rr) * CH + ch], v);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&zsum[static_cast<size_t>(f) * CH + ch]),
+                      static_cast<unsigned long long>(static_cast<long long>(mx_alt_weight(rs + rr, rows, pad)) * v));
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+        if (4 * dj[j] < cpitch)
+            *reinterpret_cast<int4*>(cpart + (static_cast<size_t>(f) * nbands + band) * cpitch + 4 * dj[j]) = make_int4(col[j][0], col[j][1], col[j][2], col[j][3]);
+}
+
+// One launch: the quirk's sums (n_alt = bands x batches x frames workgroups, none with nyquist_quirk = 0), then the edge strips
+// (strip_blocks x nstrips x frames workgroups)
+template <int CH, int G>
+__global__ __launch_bounds__(256) void fc_prepass(const uint8_t* __restrict__ src, int* __restrict__ srow, int* __restrict__ cpart, long long* __restrict__ zsum,
+                                                  uint8_t* __restrict__ strips, int rows, int cols, int pad, int pada, int nbands, int nbatches, int cpitch, int n_alt,
+                                                  int chunks, int nright, int strip_blocks, int band_rows)
+{
+    __shared__ int sred[kFcSumRows][CH][64];
+    int b = blockIdx.x;
+    if (b < n_alt) {
+        const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
+        fc_altsums_body<CH, G>(src, srow, cpart, zsum, rows, cols, pad, nbands, cpitch, band, batch, f, sred, band_rows);
+    } else {
+        b -= n_alt;
+        const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);
+        fc_edge_strips_body<CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f);
+    }
+}
 
 }  // namespace blur_amd

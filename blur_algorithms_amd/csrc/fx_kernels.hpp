@@ -1069,7 +1069,7 @@ __global__ __launch_bounds__(256) void fx_prepass(const uint8_t* __restrict__ sr
 #endif  // BLUR_FX_QUIRK_KERNELS
 
 // ---- launcher ----------------------------------------------------------------------------------------------------------
-// The task grid shared by the fused launchers (fx_launch_u8, fw_launch_u8, fc_launch_ch, ff_launch_ch; bench.py:
+// The task grid shared by the fused launchers (fx_launch_u8, fw_launch, ff_launch_ch; bench.py:
 // fused_launch_shape models it).  One task is a segment of a stripe: a strip of kFxChunk columns of one frame and, for the kernels
 // that take one channel per task, one of its nch channels.  ntasks == 0: nothing to launch.
 struct FxLaunch {

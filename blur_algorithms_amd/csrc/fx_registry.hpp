@@ -1,19 +1,32 @@
-// fx_registry.hpp -- the window sizes (NKB blocks of 16 positions) the fused matrix-core kernels are instantiated for, one
-// translation unit each: fx_kernels.hpp (three channels per workgroup) for NKB <= 11 (fx_conv_<NKB>.hip), fw_kernels.hpp (one
-// channel per workgroup) for 13 .. 23 (fw_conv_<NKB>.hip).  A kernel serves every pad <= 8 (NKB - 2).
+// fx_registry.hpp -- the window classes (NKB blocks of 16 positions) the fused matrix-core kernels are instantiated for, one
+// translation unit per class and kernel file.  A kernel serves every pad <= 8 (NKB - 2).
+//   three channels   fx_kernels.hpp (three channels per workgroup) for NKB <= 11 (fx_conv_<NKB>.hip), fw_kernels.hpp (one channel
+//                    per workgroup) for 13 .. 23 (fw_conv_<NKB>.hip): FxEntry
+//   one, four        fw_kernels.hpp for every class (fw_conv_<NKB>.hip): FcEntry
+//   float32          ff_kernels.hpp for every class (ff_conv_<NKB>.hip; ff_registry.hpp): FfEntry
 #pragma once
-#include "fx_kernels.hpp"
+#include "fw_kernels.hpp"
+#define BLUR_FX_CLASSES(X) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23)
 namespace blur_amd {
-#define BLUR_FX_DECL(NKB_) const FxEntry* fx_entry_##NKB_();
-BLUR_FX_DECL(3) BLUR_FX_DECL(5) BLUR_FX_DECL(7) BLUR_FX_DECL(9) BLUR_FX_DECL(11)
-BLUR_FX_DECL(13) BLUR_FX_DECL(15) BLUR_FX_DECL(17) BLUR_FX_DECL(19) BLUR_FX_DECL(21) BLUR_FX_DECL(23)
+#define BLUR_FX_DECL(NKB_) const FxEntry* fx_entry_##NKB_(); const FcEntry* fc_entry_##NKB_();
+BLUR_FX_CLASSES(BLUR_FX_DECL)
 #undef BLUR_FX_DECL
 inline const FxEntry* find_fx_entry(int pad)
 {
-    static const FxEntry* const list[] = { fx_entry_3(), fx_entry_5(), fx_entry_7(), fx_entry_9(), fx_entry_11(),
-                                           fx_entry_13(), fx_entry_15(), fx_entry_17(), fx_entry_19(), fx_entry_21(), fx_entry_23() };
+#define BLUR_FX_ITEM(NKB_) fx_entry_##NKB_(),
+    static const FxEntry* const list[] = { BLUR_FX_CLASSES(BLUR_FX_ITEM) };
+#undef BLUR_FX_ITEM
     for (const FxEntry* e : list)
         if (8 * (e->nkb - 2) >= pad) return e;
+    return nullptr;
+}
+inline const FcEntry* find_fc_entry(int nkb)
+{
+#define BLUR_FC_ITEM(NKB_) fc_entry_##NKB_(),
+    static const FcEntry* const list[] = { BLUR_FX_CLASSES(BLUR_FC_ITEM) };
+#undef BLUR_FC_ITEM
+    for (const FcEntry* e : list)
+        if (e->nkb == nkb) return e;
     return nullptr;
 }
 }  // namespace blur_amd

@@ -1,6 +1,6 @@
 """blur_gaussian_u8_*: argument validation that needs no device (the checks run before the context is touched, so ctx may be
-NULL), the bindings of the new entry points, and the host-side geometry of the 1- / 4-channel fused kernel's staging (fc_kernels.hpp)
-mirrored in Python."""
+NULL), the bindings of the new entry points, and the host-side geometry of the one-channel-per-workgroup fused kernel's staging and
+stores (fw_kernels.hpp: fw_blur_u8 for 1, 3 and 4 channels) mirrored in Python."""
 import ctypes as C
 
 import pytest
@@ -103,7 +103,7 @@ def test_multi_refuses_a_mismatched_out_before_the_library():
         api.BlurMulti.gaussian_f32(m, frames.astype(np.float32), 2.0, out=np.zeros((2, 8, 8, 4), np.uint8))
 
 
-# ---- host mirror of the staging geometry of fc_blur_u8 ----------------------------------------------------------------
+# ---- host mirror of the staging and store geometry of fw_blur_u8 --------------------------------------------------------
 def fw_cfg(nkb):
     pada = 8 * (nkb - 2)
     win = 128 + 2 * pada
@@ -114,12 +114,15 @@ def fw_cfg(nkb):
     return pada, win, gpr, per, cs, ips
 
 
-@pytest.mark.parametrize("nkb", [3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23])
-@pytest.mark.parametrize("ch", [1, 4])
-def test_staging_covers_the_window_once(nkb, ch):
-    """thread (row, g0) loads the groups g0 + 8 k (4 pixels = 4 ch bytes each) at byte 4 ch g0 + 32 ch k of a window row; the
-    groups past the window's last one reload group g0 (their halfs land in the row's padding); the column-pass slots 5 .. cs - 1
-    commit ips items each, which must cover all per of them"""
+# the kernel's instantiations (fw_conv_<NKB>.hip): 1 and 4 channels for every window class, 3 for the wide ones (NKB >= 13)
+FW_KERNELS = [(ch, nkb) for ch in (1, 3, 4) for nkb in (3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23) if ch != 3 or nkb >= 13]
+
+
+@pytest.mark.parametrize("ch, nkb", FW_KERNELS)
+def test_staging_covers_the_window_once(ch, nkb):
+    """thread (row, g0) loads the groups g0 + 8 k (4 pixels = 4 ch bytes each; ch = 3: twelve-byte groups at 12 g0 + 96 k) at byte
+    4 ch g0 + 32 ch k of a window row; the groups past the window's last one reload group g0 (their halfs land in the row's
+    padding); the column-pass slots 5 .. cs - 1 commit ips items each, which must cover all per of them"""
     pada, win, gpr, per, cs, ips = fw_cfg(nkb)
     assert ips * (cs - 5) >= per
     seen = {}
@@ -137,10 +140,10 @@ def test_staging_covers_the_window_once(nkb, ch):
     assert 4 * 7 + 32 * (per - 1) + 4 <= 32 * per
 
 
-@pytest.mark.parametrize("ch", [1, 4])
+@pytest.mark.parametrize("ch", [1, 3, 4])
 def test_output_stores_stay_in_the_frame(ch):
     """CH = 1: lane q of quad Q stores pixels 4 Q .. 4 Q + 3 of row 8 gq + 4 h + q as one dword when all four lie in the image,
-    else (ragged widths) bytes for the ones that do; CH = 4: byte c of the lane's pixel.  Every pixel of a tile is stored once."""
+    else (ragged widths) bytes for the ones that do; CH = 3, 4: byte c of the lane's pixel.  Every pixel of a tile is stored once."""
     for cols in (1, 2, 3, 4, 5, 127, 128, 129, 130, 131, 517):
         for x0 in range(0, cols, 128):
             written = {}
@@ -158,5 +161,29 @@ def test_output_stores_stay_in_the_frame(ch):
                         written[x] = written.get(x, 0) + 1
             want = set(range(x0, min(x0 + 128, cols)))
             assert set(written) == want
-            # CH = 1: the four lanes of a quad store the same pixels, each in its own row; CH = 4: one lane per pixel
+            # CH = 1: the four lanes of a quad store the same pixels, each in its own row; CH = 3, 4: one lane per pixel
             assert set(written.values()) == {4 if ch == 1 else 1}
+
+
+@pytest.mark.parametrize("ch", [3, 4])
+def test_byte_store_offsets(ch):
+    """CH = 3, 4: the byte of (row 32 tile + 8 gq + 4 h + k, pixel xcol, channel c) goes to (row cols + xcol) ch + c, whether the
+    kernel adds the row group's offset to the lane's offset in row 4 h (CH = 3) or computes it whole (CH = 4); in-frame bytes lie
+    inside the output resource (rows cols ch bytes)"""
+    rows, cols = 70, 131
+    size = rows * cols * ch
+    rowstep = cols * ch
+    for c in range(ch):
+        for xcol in (0, 1, 127, 128, 130):
+            for h in (0, 1):
+                lane_out = (4 * h * cols + xcol) * ch + c
+                for tile in (0, 1, 2):
+                    for gq in range(4):
+                        row0 = 32 * tile + 8 * gq + 4 * h
+                        split = lane_out + (32 * tile + 8 * gq) * rowstep
+                        whole = (row0 * cols + xcol) * ch + c
+                        assert split == whole
+                        for k in range(4):
+                            if row0 + k < rows:
+                                o = whole + k * rowstep
+                                assert o == ((row0 + k) * cols + xcol) * ch + c and o < size

@@ -1,6 +1,6 @@
 """Gaussian blur of 1- and 4-channel u8 images (blur_gaussian_u8_*): every channel blurred on its own as pffft_() blurs one of its
 three, checked against the float64 oracle per channel plane under the parity contract, across every window class of the fused
-kernel (fc_kernels.hpp), the plane fallback, ragged and edge-strip widths, unaligned pointers, batches and the multi-shard entry."""
+kernel (fw_kernels.hpp), the plane fallback, ragged and edge-strip widths, unaligned pointers, batches and the multi-shard entry."""
 import ctypes as C
 
 import numpy as np

@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/fw_variants.sh "name|flags" ... -- on the GPU box: the wide fused kernels (fw_conv_*.hip) rebuilt with extra flags as a scratch
+# tools/fw_variants.sh "name|flags" ... -- on the GPU box: the wide fused kernels (fw_conv_13 .. 23.hip) rebuilt with extra flags as a scratch
 # library under variants/ (tools/variant.sh; the repo's own build is not touched), timed with tools/fw_dev.py --no-check $FW_DEV_ARGS
 for spec in "$@"; do
     name=${spec%%|*}; flags=${spec#*|}
