@@ -1836,22 +1836,50 @@ static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nfram
 }
 
 // the plane fallback: split a frame into f32 planes, blur each on the f32 plane path, interleave the results
-template <typename T>
-__global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes, size_t px, int ch)
+// Float frames are scaled by a power of two on the way in and back on the way out (exact), as the fused kernel scales its frames:
+// the plane path's transforms are unnormalised f32, so max|x| near 1e37 overflowed in them and max|x| near 1e-37 lost bits to
+// subnormals.  mbits: the bits of max|x| over the frame (an integer atomicMax: the same result in any order); the scale puts
+// max|x| into [0.5, 1).  u8 frames are not scaled (mbits is not read).
+__global__ void chan_maxabs(const float* __restrict__ src, unsigned* __restrict__ mbits, size_t n)
 {
-    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        for (int c = 0; c < ch; ++c) planes[c * px + i] = static_cast<float>(src[i * ch + c]);
+    unsigned m = 0;
+    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * blockDim.x)
+        m = max(m, __float_as_uint(src[i]) & 0x7fffffffu);
+    if (m) atomicMax(mbits, m);
+}
+
+__device__ inline int chan_scale_exp(unsigned mbits)
+{
+    const float m = __uint_as_float(mbits);
+    if (!(m > 0.f) || mbits >= 0x7f800000u) return 0;              // zero frame, Inf or NaN: no scale
+    int k = 0;
+    (void)frexpf(m, &k);                                            // m = f 2^k, f in [0.5, 1)
+    return -k < -125 ? -125 : (-k > 125 ? 125 : -k);                // 2^e and 2^-e stay normal floats
 }
 
 template <typename T>
-__global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst, size_t px, int ch)
+__global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes, size_t px, int ch, const unsigned* __restrict__ mbits)
 {
+    float scale = 1.f;
+    if constexpr (std::is_same_v<T, float>) scale = ldexpf(1.f, chan_scale_exp(*mbits));
+    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
+        for (int c = 0; c < ch; ++c) {
+            if constexpr (std::is_same_v<T, float>) planes[c * px + i] = src[i * ch + c] * scale;
+            else planes[c * px + i] = static_cast<float>(src[i * ch + c]);
+        }
+}
+
+template <typename T>
+__global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst, size_t px, int ch, const unsigned* __restrict__ mbits)
+{
+    float unscale = 1.f;
+    if constexpr (std::is_same_v<T, float>) unscale = ldexpf(1.f, -chan_scale_exp(*mbits));
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
         for (int c = 0; c < ch; ++c) {
             if constexpr (std::is_same_v<T, uint8_t>)  // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
                 dst[i * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffu);
             else
-                dst[i * ch + c] = planes[c * px + i];
+                dst[i * ch + c] = planes[c * px + i] * unscale;
         }
 }
 
@@ -1862,19 +1890,25 @@ static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int 
     if (int rc = prepare(ctx, rows, cols, sigma, opts, p, false)) return rc;
     const size_t px = static_cast<size_t>(rows) * cols;
     if (int rc = ensure_work(ctx, px * sizeof(float))) return rc;
-    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_planes), &ctx->ch_planes_bytes, px * ch * sizeof(float))) return rc;
+    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_planes), &ctx->ch_planes_bytes, px * ch * sizeof(float) + 16)) return rc;
+    unsigned* mbits = reinterpret_cast<unsigned*>(ctx->ch_planes + px * ch);          // behind the planes
     const unsigned blocks = static_cast<unsigned>(std::min<size_t>((px + 255) / 256, 4096));
     for (int f = 0; f < nframes; ++f) {
         const T* s = d_src + static_cast<size_t>(f) * px * ch;
         T* d = d_dst + static_cast<size_t>(f) * px * ch;
-        hipLaunchKernelGGL(chan_split<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch);
+        if constexpr (std::is_same_v<T, float>) {
+            HIP_TRY(ctx, hipMemsetAsync(mbits, 0, sizeof(unsigned), ctx->stream));
+            hipLaunchKernelGGL(chan_maxabs, dim3(blocks), dim3(256), 0, ctx->stream, s, mbits, px * ch);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(chan_split<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch, mbits);
         HIP_TRY(ctx, hipGetLastError());
         for (int c = 0; c < ch; ++c) {
             float* plane = ctx->ch_planes + c * px;
             if (int rc = launch_rowpass<float, 1>(ctx, plane, ctx->work, rows, cols, p.sz.pad, *p.row, p.m_row)) return rc;
             if (int rc = launch_colpass<float, 1>(ctx, ctx->work, plane, rows, cols, p.sz.pad, *p.col, p.m_col, p.col_group)) return rc;
         }
-        hipLaunchKernelGGL(chan_pack<T>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch);
+        hipLaunchKernelGGL(chan_pack<T>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch, mbits);
         HIP_TRY(ctx, hipGetLastError());
     }
     return BLUR_OK;
@@ -1893,7 +1927,7 @@ static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nf
 }
 
 // One driver for both element types.  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused kernel
-// for NKB 23 with 3 or 4 channels (ff_class_ok); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 /
+// for NKB 23 with 3 or 4 channels (ff_class_ok) and its own choice stops at NKB 15 (ff_class_in_contract); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 /
 // run_ff_f32) and the engine error's text
 template <typename T>
 static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
@@ -1926,6 +1960,8 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
         } else if (rc) return rc;
         const char* why = nullptr;
         if (p.fx && f32 && !ff_class_ok(p.fx->nkb, channels)) why = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
+        else if (p.fx && f32 && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(p.fx->nkb))
+            why = "fused kernel for float32 images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED";
         else if (p.fx && static_cast<long long>(rows) * cols * channels * static_cast<long long>(sizeof(T)) > 0xfffff000ll)
             why = "fused matrix-core engine: frame too large for 32-bit offsets";
         if (why) {

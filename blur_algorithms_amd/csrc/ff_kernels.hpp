@@ -385,6 +385,11 @@ __global__ __launch_bounds__(256, 1) void ff_blur_f32(const float* __restrict__ 
 // The classes that are instantiated: all but NKB = 23 with 3 or 4 channels, whose strided loads leave no registers for the window
 // (768 bytes of scratch per lane); those take the plane fallback
 __host__ __device__ constexpr bool ff_class_ok(int nkb, int ch) { return !(nkb >= 23 && ch != 1); }
+// The classes the library's own choice takes.  The f32 accumulation over 2 x 3 products per window block reaches 1.02e-6 (NKB 19)
+// and 1.11e-6 (NKB 21, 23) of max|x| where the output is as large as max|x| over an area (steps, constants), and 1.19e-6 at NKB 17
+// with max|x| = 0.7e30, past the contract's 1e-6; NKB <= 15 was measured within it (9.0e-7).  AUTO takes the plane fallback for pad
+// 105 .. 168; FUSED still runs the kernel.
+__host__ __device__ constexpr bool ff_class_in_contract(int nkb) { return nkb <= 15; }
 
 struct FfEntry {
     int nkb;

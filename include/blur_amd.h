@@ -177,9 +177,12 @@ int blur_gaussian_u8_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int r
    (4-byte aligned; any float offset).  Every channel is blurred on its own exactly as pffft_() blurs one of its planes (sizing and
    kernel from (rows, cols, sigma), reflect-101, the Nyquist-slot quirk per channel plane unless opts->nyquist_quirk = 0) and the
    result is the float plane as blur_gaussian_f32c1_dev returns it: no + 0.5f truncation, no clamping.  Parity: |got - float64
-   reference| <= 1e-6 max|x| of the frame, per pixel and channel.  opts->engine AUTO takes the fused matrix-core kernel wherever it
-   applies (pad <= 168; pad 153 .. 168 for 1 channel only; frames of at most 4 GiB - 4 KiB), the f32 plane path per channel
-   elsewhere; FUSED fails with BLUR_ERR_UNSUPPORTED where the fused kernel does not apply; FFT always takes the plane path; other
+   reference| <= 1e-6 max|x| of the frame, per pixel and channel, under AUTO and FFT.  opts->engine AUTO takes the fused matrix-core
+   kernel for pad <= 104 (frames of at most 4 GiB - 4 KiB), the f32 plane path per channel elsewhere; FUSED runs the fused kernel
+   wherever one exists (pad <= 168; pad 153 .. 168 for 1 channel only) and fails with BLUR_ERR_UNSUPPORTED elsewhere: for pad
+   105 .. 168 it is outside the parity bound where the output is as large as max|x| over an area (measured 1.19e-6 max|x| on step
+   images; within the bound on noise), which is why AUTO does not take it there; FFT always takes the plane path, which scales each frame by a power of two as the fused
+   kernel does (measured within the bound from max|x| = 0.7e-37 to 0.7e37); other
    engines are BLUR_ERR_UNSUPPORTED.  blur_last_engine reports 6 (fused) or 0 (plane path).  The call is asynchronous on the
    context's stream.  Results are bit-reproducible: a frame gives the same bits alone and inside a batch.  d_dst may equal d_src;
    other overlaps are detected over the whole batch and read from a copy.  Inputs holding NaN or +-Inf give unspecified output
