@@ -123,9 +123,9 @@ _gauss_f32_frames_shape = _gauss_frames_shape      # (the float32 entry points' 
 
 def _gauss_array(image, out, dtype, batch=False):
     """the host arrays of a per-channel Gaussian call: (source, result, (n, rows, cols, C)).  uint8 input of another dtype is
-    converted, as pffft_ does; float32 input must be float32.  batch: frames [n, rows, cols, C] only"""
-    if dtype == np.float32 and image.dtype != np.float32:
-        raise ValueError("expected a float32 array")
+    converted, as pffft_ does; float32 input must be float32 and uint16 input uint16.  batch: frames [n, rows, cols, C] only"""
+    if dtype != np.uint8 and image.dtype != dtype:
+        raise ValueError("expected a %s array" % np.dtype(dtype).name)
     a = np.ascontiguousarray(image, dtype)
     if batch and a.ndim != 4:
         raise ValueError("expected %s frames [n, rows, cols, C]" % np.dtype(dtype).name)
@@ -140,7 +140,7 @@ def _gauss_tensor(image, out, dtype, device=None):
     """the CUDA tensors of a per-channel Gaussian call: (source, result (default: the source), (n, rows, cols, C)).  device: frames
     [n, rows, cols, C] on that device only"""
     import torch
-    want = torch.uint8 if dtype == np.uint8 else torch.float32
+    want = {np.uint8: torch.uint8, np.uint16: torch.uint16, np.float32: torch.float32}[dtype]
     t = image
     if (not isinstance(t, torch.Tensor) or t.dtype != want or not t.is_cuda or not t.is_contiguous()
             or (device is not None and (t.dim() != 4 or t.device.index != device))):
@@ -504,6 +504,17 @@ class BlurContext:
         return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.float32, self._lib.blur_gaussian_f32_host,
                               self._lib.blur_gaussian_f32_batch_dev)
 
+    def gaussian_u16(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
+        """Gaussian blur of a uint16 image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows, cols, C].  Every
+        channel is blurred on its own as pffft_ blurs one of its planes; the float result v leaves as (v + 0.5) truncated, low 16
+        bits kept: no clamping (blur_gaussian_u16_batch_dev).  engine: None (the library's choice), "fused" or "fft".
+
+        torch CUDA tensor (torch.uint16): asynchronous on torch's current stream, returns `out` (default: in place).  numpy array:
+        host round trip, returns a new array.
+        """
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.uint16, self._lib.blur_gaussian_u16_host,
+                              self._lib.blur_gaussian_u16_batch_dev)
+
     def _gaussian(self, image, sigma, out, nyquist_quirk, engine, dtype, host_entry, batch_dev_entry):
         o = self._opts(nyquist_quirk, engine=engine)
         if isinstance(image, np.ndarray):
@@ -613,6 +624,12 @@ class BlurMulti:
         tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
         return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.float32, self._lib.blur_gaussian_f32_batch_multi_host,
                               self._lib.blur_gaussian_f32_batch_multi_dev)
+
+    def gaussian_u16(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
+        """BlurContext.gaussian_u16 over a batch sharded by frame: frames uint16 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
+        tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.uint16, self._lib.blur_gaussian_u16_batch_multi_host,
+                              self._lib.blur_gaussian_u16_batch_multi_dev)
 
     def _gaussian(self, frames, sigma, out, nyquist_quirk, engine, dtype, multi_host_entry, multi_dev_entry):
         o = BlurOpts()

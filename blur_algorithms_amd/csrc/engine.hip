@@ -768,9 +768,9 @@ struct blur_ctx {
     size_t ch_planes_bytes = 0;
     uint8_t* ch_copy = nullptr;      // 1- / 4-channel images: a copy of overlapping source frames
     size_t ch_copy_bytes = 0;
-    void* ff_sums = nullptr;         // float32 images, fused kernel: max|x| per frame and the quirk's sums (run_ff_f32)
+    void* ff_sums = nullptr;         // float32 / u16 images, fused kernel: max|x| per frame (float) and the quirk's sums (run_ff)
     size_t ff_sums_bytes = 0;
-    float* ff_strips = nullptr;      // float32 images, fused kernel: the edge chunks' windows
+    void* ff_strips = nullptr;       // float32 / u16 images, fused kernel: the edge chunks' windows (samples of the frame's type)
     size_t ff_strips_bytes = 0;
     size_t box_bytes = 0;
     std::string engine_note;      // BLUR_ENGINE_AUTO: why the last call's choice passed over a faster engine ("" if it did not)
@@ -1699,8 +1699,9 @@ static int run_colpass_u8c3(blur_ctx* ctx, const float* planes, uint8_t* dst, in
 }
 
 // ======================================================================================
-// 1- and 4-channel u8 images (blur_gaussian_u8_*) and float32 images of 1, 3 or 4 channels (blur_gaussian_f32_*): every channel
-// blurred on its own as pffft_() blurs one of its planes (u8 with the + 0.5f truncation, float32 without)
+// 1- and 4-channel u8 images (blur_gaussian_u8_*), float32 and u16 images of 1, 3 or 4 channels (blur_gaussian_f32_*,
+// blur_gaussian_u16_*): every channel blurred on its own as pffft_() blurs one of its planes (u8 and u16 with the + 0.5f truncation,
+// float32 without)
 // ======================================================================================
 #include "ff_registry.hpp"
 
@@ -1774,23 +1775,31 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
 // the fused kernel (ff_kernels.hpp): the pre-pass (max|x|, the quirk's sums, the edge chunks' strips), the quirk's finalisation,
 // then the kernel.  Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).  Every
 // partition of a sum (bands, batches) depends on the frame's shape only: a frame gives the same bits alone and in a batch.
-static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
+// T = float or uint16_t.  u16: no max|x| (the scale is a constant of the call), and without the quirk no sums at all.
+template <typename T>
+static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
 {
+    constexpr bool u16 = std::is_same_v<T, uint16_t>;
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
-    const FfEntry* fe = find_ff_entry(nkb);
-    if (!fe || !ff_class_ok(nkb, ch)) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for float32 images: no kernel instantiated for this pad and channel count");
+    const FfEntryT<T>* fe = nullptr;
+    if constexpr (u16) fe = find_ff_u16_entry(nkb);
+    else fe = find_ff_entry(nkb);
+    if (!fe || !ff_class_ok_t<T>(nkb, ch))
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, u16 ? "fused kernel for u16 images: no kernel instantiated for this pad and channel count"
+                                                   : "fused kernel for float32 images: no kernel instantiated for this pad and channel count");
     FxGeom g{ rows, cols, p.sz.pad, nframes, 0, (rows + 31) / 32, fx_right_strips(cols, pada), ctx->num_xcds };
     const int chunks_x = (cols + kFxChunk - 1) / kFxChunk, win = kFxChunk + 2 * pada, nstrips = fx_left_strips(pada) + g.nright;
-    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ff_strips), &ctx->ff_strips_bytes,
-                            (static_cast<size_t>(nframes) * nstrips * rows * win * ch + 16) * sizeof(float))) return rc;
+    if (int rc = ensure_buf(ctx, &ctx->ff_strips, &ctx->ff_strips_bytes,
+                            (static_cast<size_t>(nframes) * nstrips * rows * win * ch + 16) * sizeof(T))) return rc;
+    T* strips = static_cast<T*>(ctx->ff_strips);
     const int strip_blocks = static_cast<int>((static_cast<long long>(rows) * ch * win + 255) / 256);
     const int n_strip = strip_blocks * nstrips * nframes;
     const int G = ff_groups_per_thread(cols, ch), ne = cols * ch, nbatches = (ne + ff_batch_stride(ch) * G - 1) / (ff_batch_stride(ch) * G);
     // bands of rows: enough workgroups per frame to read it at the memory's rate (from the frame's shape alone)
     int band_rows = 16;
     while (band_rows < 128 && static_cast<long long>(nbatches) * ((rows + 2 * band_rows - 1) / (2 * band_rows)) >= 512) band_rows *= 2;
-    const int nbands = (rows + band_rows - 1) / band_rows, n_alt = nbands * nbatches * nframes;
     const bool quirk = p.mx_quirk;
+    const int nbands = (rows + band_rows - 1) / band_rows, n_alt = u16 && !quirk ? 0 : nbands * nbatches * nframes;
     // [mbits: frames][zsum: frames x ch][srow: frames x rows x ch][spart: frames x batches x rows x ch][cpart: frames x bands x ne]
     const size_t n_m = (static_cast<size_t>(nframes) + 1) / 2, n_z = static_cast<size_t>(nframes) * ch, n_srow = static_cast<size_t>(nframes) * rows * ch;
     const size_t n_spart = quirk ? n_srow * nbatches : 0, n_cpart = quirk ? static_cast<size_t>(nframes) * nbands * ne : 0;
@@ -1801,9 +1810,9 @@ static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nfram
     double* srow = zsum + n_z;
     double* spart = srow + (quirk ? n_srow : 0);
     double* cpart = spart + n_spart;
-    HIP_TRY(ctx, hipMemsetAsync(mbits, 0, static_cast<size_t>(nframes) * sizeof(unsigned), ctx->stream));
+    if (!u16) HIP_TRY(ctx, hipMemsetAsync(mbits, 0, static_cast<size_t>(nframes) * sizeof(unsigned), ctx->stream));
     FfQuirk qk{};
-    qk.mbits = mbits;
+    qk.mbits = u16 ? nullptr : mbits;
     qk.bscale = 1.0;
     if (quirk) {
         qk.srow = srow;
@@ -1819,10 +1828,12 @@ static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nfram
     {
         TimedLaunch t(ctx, 1, nframes);
         auto pick = [&](auto k1, auto k2, auto k4) { return G == 1 ? k1 : (G == 2 ? k2 : k4); };
-        auto kern = ch == 1 ? pick(ff_prepass<1, 1>, ff_prepass<1, 2>, ff_prepass<1, 4>)
-                            : (ch == 3 ? pick(ff_prepass<3, 1>, ff_prepass<3, 2>, ff_prepass<3, 4>) : pick(ff_prepass<4, 1>, ff_prepass<4, 2>, ff_prepass<4, 4>));
-        hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, mbits, spart, cpart, ctx->ff_strips, rows, cols, p.sz.pad, pada, nbands,
-                           nbatches, ne, n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0);
+        auto kern = ch == 1 ? pick(ff_prepass<T, 1, 1>, ff_prepass<T, 1, 2>, ff_prepass<T, 1, 4>)
+                            : (ch == 3 ? pick(ff_prepass<T, 3, 1>, ff_prepass<T, 3, 2>, ff_prepass<T, 3, 4>)
+                                       : pick(ff_prepass<T, 4, 1>, ff_prepass<T, 4, 2>, ff_prepass<T, 4, 4>));
+        if (n_alt + n_strip > 0)
+            hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, mbits, spart, cpart, strips, rows, cols, p.sz.pad, pada, nbands,
+                               nbatches, ne, n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0);
         HIP_TRY(ctx, hipGetLastError());
         if (quirk) {
             auto fin = ch == 1 ? ff_finalize<1> : (ch == 3 ? ff_finalize<3> : ff_finalize<4>);
@@ -1831,7 +1842,7 @@ static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nfram
         }
     }
     TimedLaunch t(ctx, 0, nframes);
-    HIP_TRY(ctx, fe->blur_f32(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, ctx->ff_strips));
+    HIP_TRY(ctx, fe->blur(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, strips));
     return BLUR_OK;
 }
 
@@ -1839,7 +1850,7 @@ static int run_ff_f32(blur_ctx* ctx, const float* d_src, float* d_dst, int nfram
 // Float frames are scaled by a power of two on the way in and back on the way out (exact), as the fused kernel scales its frames:
 // the plane path's transforms are unnormalised f32, so max|x| near 1e37 overflowed in them and max|x| near 1e-37 lost bits to
 // subnormals.  mbits: the bits of max|x| over the frame (an integer atomicMax: the same result in any order); the scale puts
-// max|x| into [0.5, 1).  u8 frames are not scaled (mbits is not read).
+// max|x| into [0.5, 1).  u8 and u16 frames are not scaled (mbits is not read).
 __global__ void chan_maxabs(const float* __restrict__ src, unsigned* __restrict__ mbits, size_t n)
 {
     unsigned m = 0;
@@ -1878,6 +1889,8 @@ __global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst,
         for (int c = 0; c < ch; ++c) {
             if constexpr (std::is_same_v<T, uint8_t>)  // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
                 dst[i * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffu);
+            else if constexpr (std::is_same_v<T, uint16_t>)  // the same rule 16 bits wide: truncate, keep the low 16 bits
+                dst[i * ch + c] = static_cast<uint16_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffffu);
             else
                 dst[i * ch + c] = planes[c * px + i] * unscale;
         }
@@ -1914,7 +1927,7 @@ static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int 
     return BLUR_OK;
 }
 
-// the arguments of every blur_gaussian_{u8,f32}_* entry, without the device (ctx may be NULL here: the status is the same)
+// the arguments of every blur_gaussian_{u8,f32,u16}_* entry, without the device (ctx may be NULL here: the status is the same)
 static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nframes, int rows, int cols, int channels, double sigma)
 {
     if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
@@ -1926,20 +1939,22 @@ static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nf
     return ctx ? BLUR_OK : BLUR_ERR_INVALID;
 }
 
-// One driver for both element types.  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused kernel
-// for NKB 23 with 3 or 4 channels (ff_class_ok) and its own choice stops at NKB 15 (ff_class_in_contract); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 /
-// run_ff_f32) and the engine error's text
+// One driver for the three element types.  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused
+// kernel for NKB 23 with 3 or 4 channels (ff_class_ok_t); the own choice of float32 and u16 stops at NKB 15 (ff_class_in_contract: at 16 bits
+// 1e-6 of full scale is 0.066 of a grey level); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 / run_ff<T>)
+// and the engine error's text
 template <typename T>
 static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
 {
-    constexpr bool f32 = std::is_same_v<T, float>;
+    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, ffk = !u8;      // ffk: the ff_kernels.hpp types
     if (int rc = check_ch_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma)) return rc;
-    if constexpr (!f32) {
+    if constexpr (u8) {
         if (channels == 3) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
     }
     const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
     if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, f32 ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT");
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, u16 ? "u16 images: engine must be AUTO, FUSED or FFT"
+                                                   : (ffk ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT"));
     // The fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED: a kernel for the pad, the frame and quirk limits; a
     // float32 class instantiated for the channel count; the frame's bytes within 32-bit offsets), the plane fallback elsewhere.  AUTO
     // too: where the u8c3 policy passes the fused engine over for a compile-time FFT family (frames under 1 MP, pad > 152 on 6 MP), the
@@ -1959,9 +1974,10 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
             ctx->err.clear();                    // (not a failure of this call)
         } else if (rc) return rc;
         const char* why = nullptr;
-        if (p.fx && f32 && !ff_class_ok(p.fx->nkb, channels)) why = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
-        else if (p.fx && f32 && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(p.fx->nkb))
-            why = "fused kernel for float32 images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED";
+        if (p.fx && ffk && !ff_class_ok_t<T>(p.fx->nkb, channels)) why = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
+        else if (p.fx && ffk && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(p.fx->nkb))
+            why = u16 ? "fused kernel for u16 images: pad 105 .. 168 exceeds 1e-6 of full scale on full-scale content (1.2e-6); ask for it with engine = FUSED"
+                      : "fused kernel for float32 images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED";
         else if (p.fx && static_cast<long long>(rows) * cols * channels * static_cast<long long>(sizeof(T)) > 0xfffff000ll)
             why = "fused matrix-core engine: frame too large for 32-bit offsets";
         if (why) {
@@ -1996,7 +2012,7 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
     }
     if (p.fx) {
         ctx->last_family = 6;
-        if constexpr (f32) return run_ff_f32(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
+        if constexpr (ffk) return run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
         else return run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
     }
     blur_opts o;
@@ -2009,7 +2025,7 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
     return BLUR_OK;
 }
 
-// blur_gaussian_{u8,f32}_host: one frame through the context's host staging buffer (source and destination apart: no in-place copy)
+// blur_gaussian_{u8,f32,u16}_host: one frame through the context's host staging buffer (source and destination apart: no in-place copy)
 template <typename T>
 static int blur_ch_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
 {
@@ -3338,7 +3354,7 @@ int blur_fastboxblur_u8_batch_multi_host(blur_multi* m, uint8_t* inout, int nfra
     return box_multi(m, inout, nframes, w, h, channels, ksize, passes, 0);
 }
 
-// blur_gaussian_{u8,f32}_batch_multi_*: the frames of a batch sharded over the devices (a template: C++ linkage)
+// blur_gaussian_{u8,f32,u16}_batch_multi_*: the frames of a batch sharded over the devices (a template: C++ linkage)
 extern "C++" {
 template <typename T>
 static int blur_ch_multi(blur_multi* m, const T* src, T* dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts, int location)
@@ -3410,6 +3426,35 @@ int blur_gaussian_f32_batch_multi_dev(blur_multi* m, const float* d_src, float* 
 }
 
 int blur_gaussian_f32_batch_multi_host(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels, double sigma,
+                                       const blur_opts* opts)
+{
+    return blur_ch_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
+}
+
+// u16 images of 1, 3 or 4 channels
+int blur_gaussian_u16_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                const blur_opts* opts)
+{
+    return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_u16_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_ch_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_u16_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_ch_host(ctx, src, dst, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_u16_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                      const blur_opts* opts)
+{
+    return blur_ch_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, 1);
+}
+
+int blur_gaussian_u16_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels, double sigma,
                                        const blur_opts* opts)
 {
     return blur_ch_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);

@@ -1,4 +1,4 @@
-// ff_kernels.hpp -- the fused matrix-core kernel for float32 images of 1, 3 or 4 channels, every window class (NKB = 3 .. 23
+// ff_kernels.hpp -- the fused matrix-core kernel for float32 and u16 images of 1, 3 or 4 channels, every window class (NKB = 3 .. 23
 // blocks of 16 positions: pad <= 168).
 //
 // The structure is fw_kernels.hpp's: a workgroup handles ONE channel of a strip of 128 pixel columns (channel fastest in the task
@@ -18,7 +18,22 @@
 //   * the quirk's sums are floating point: f32 products summed in double, every reduction in a fixed order (no float atomics), so
 //     a frame gives the same bits alone and inside a batch.
 // The accumulator budget is fw_kernels.hpp's: (NKB - 1) / 2 <= 11 tiles of one channel.
+//
+// The kernel is a template over the pixel type T: float32, or u16 (blur_gaussian_u16_*).  What a u16 input changes, and nothing else:
+//   * range: known from the type, so the scale is a constant of the call, e = ff_scale_exp(65535, B): no max|x| pass, no mbits;
+//   * staging: a u16 sample splits EXACTLY into hi + lo (16 bits into 11 + 5), so the dropped x_lo t_lo is the row pass's only
+//     truncation, as for floats;
+//   * loads: CH = 1 one 8-byte load per group of 4 pixels (two registers per group where the float kernel holds four); CH = 3 / 4
+//     the channel's four strided 16-bit loads.  Loads from the image stay inside a row (the edge chunks read strips), so none
+//     leaves the buffer resource whatever the row's byte count;
+//   * emission: (uint16_t)((uint32_t)(int32_t)(v + 0.5f) & 0xffff) of the float result v: add 0.5, truncate, keep the low 16 bits, no
+//     clamping (chan_pack<uint8_t>'s rule, 16 bits wide), one 16-bit store per lane and output row at stride CH.  (CH = 1: dword
+//     stores after a lane-pair exchange were measured 4 % slower than the shorts: DESIGN.md section 2.3);
+//   * the quirk's sums: the same code as for floats.  Every term is an integer below 2^53 in a double (|Z| <= 4 x 65535 rows cols,
+//     and a frame's bytes fit 32 bits), so every sum is exact and the same in any order; no limit beyond the frame limit follows.
 #pragma once
+#include <cstdint>
+#include <type_traits>
 #include "fw_kernels.hpp"
 
 namespace blur_amd {
@@ -102,11 +117,14 @@ __device__ __forceinline__ void ff_quirk_cols_tile(unsigned char* scratch, float
 }
 
 // One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
-template <int NKB, bool QUIRK, int CH>
-__global__ __launch_bounds__(256, 1) void ff_blur_f32(const float* __restrict__ src, float* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
-                                                      int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const float* __restrict__ strips)
+template <typename T, int NKB, bool QUIRK, int CH>
+__global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
+                                                  int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips)
 {
     static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
+    static_assert(std::is_same_v<T, float> || std::is_same_v<T, uint16_t>, "float32 or u16 pixels");
+    constexpr bool U16 = std::is_same_v<T, uint16_t>;
+    constexpr uint32_t ES = sizeof(T);                              // bytes per sample
     using C = FfCfg<NKB>;
     constexpr int PADA = C::PADA, PW = C::PW, NT = C::NT, PER = C::PER;
     constexpr int RS = NKB;                                        // row-pass slots
@@ -120,11 +138,11 @@ __global__ __launch_bounds__(256, 1) void ff_blur_f32(const float* __restrict__ 
     const int c = task % CH, xc = (task / CH) % chunks, seg = (task / (CH * chunks)) % nseg, f = task / (CH * chunks * nseg);
     const int x0 = xc * kFxChunk;
     const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
-    const float* img = src + static_cast<size_t>(f) * g.rows * g.cols * CH;
-    float* out = dst + static_cast<size_t>(f) * g.rows * g.cols * CH;
+    const T* img = src + static_cast<size_t>(f) * g.rows * g.cols * CH;
+    T* out = dst + static_cast<size_t>(f) * g.rows * g.cols * CH;
 
-    // the frame's scale (ff_scale_exp): s = 2^e on the staged values, 2^-e on the results
-    const int sexp = ff_scale_exp(__uint_as_float(qk.mbits[f]), qk.bscale);
+    // the frame's scale (ff_scale_exp): s = 2^e on the staged values, 2^-e on the results (u16: from the type's range, mbits is not read)
+    const int sexp = U16 ? ff_scale_exp(65535.f, qk.bscale) : ff_scale_exp(__uint_as_float(qk.mbits[f]), qk.bscale);
     const float scale = ldexpf(1.f, sexp), unscale = ldexpf(1.f, -sexp);
 
     constexpr int TLR = FW_TL_REGS < NKB ? FW_TL_REGS : NKB;
@@ -164,24 +182,35 @@ __global__ __launch_bounds__(256, 1) void ff_blur_f32(const float* __restrict__ 
     constexpr int NLEFT = fx_left_strips(PADA);
     const int sidx = xc < NLEFT ? xc : (xc >= chunks - g.nright ? NLEFT + xc - (chunks - g.nright) : -1);      // uniform
     // byte offsets: a frame's bytes fit 32 bits (the engine's frame limit)
-    const uint32_t pitch = sidx >= 0 ? static_cast<uint32_t>(4 * CH * C::WIN) : 4u * CH * static_cast<uint32_t>(g.cols);
-    const float* wbase = sidx >= 0 ? strips + (static_cast<size_t>(f) * (NLEFT + g.nright) + sidx) * g.rows * (CH * C::WIN) : img + CH * (x0 - PADA);
-    const uint32_t wbytes = sidx >= 0 ? static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(4 * CH * C::WIN)
-                                      : (static_cast<uint32_t>(g.rows) * g.cols - static_cast<uint32_t>(x0 - PADA)) * static_cast<uint32_t>(4 * CH);
-    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), 0, wbytes, kMxRsrcWord3);
+    const uint32_t pitch = sidx >= 0 ? static_cast<uint32_t>(ES * CH * C::WIN) : ES * CH * static_cast<uint32_t>(g.cols);
+    const T* wbase = sidx >= 0 ? strips + (static_cast<size_t>(f) * (NLEFT + g.nright) + sidx) * g.rows * (CH * C::WIN) : img + CH * (x0 - PADA);
+    const uint32_t wbytes = sidx >= 0 ? static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(ES * CH * C::WIN)
+                                      : (static_cast<uint32_t>(g.rows) * g.cols - static_cast<uint32_t>(x0 - PADA)) * static_cast<uint32_t>(ES * CH);
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wbase), 0, wbytes, kMxRsrcWord3);
     const int srow = 8 * (tid >> 6) + ((tid >> 4) & 3) + 4 * ((tid >> 3) & 1), g0 = tid & 7;      // (fx_kernels.hpp: the staging map)
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    uint32_t raw[PER][4];
+    constexpr int NR = U16 && CH == 1 ? 2 : 4;                     // u16, 1 channel: a group's 4 samples in 2 registers
+    uint32_t raw[PER][NR];
     double qv = 0.0;
     // the window of step s: thread t moves channel c of the groups of 4 pixels g0 + 8 k of row srow, all requested at once
     auto issue_window = [&](int s) __attribute__((always_inline)) {
         const int r = mx_refl(32 * s - PADA + srow, g.rows);
-        const uint32_t off = static_cast<uint32_t>(r) * pitch + static_cast<uint32_t>(16 * CH * g0 + 4 * c);
+        const uint32_t off = static_cast<uint32_t>(r) * pitch + ES * static_cast<uint32_t>(4 * CH * g0 + c);
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const bool in = (C::GPR % 8 == 0) || k < PER - 1 || g0 < C::GPR % 8;
-            const uint32_t o = in ? off + static_cast<uint32_t>(128 * CH * k) : off;
-            if (CH == 1) {
+            const uint32_t o = in ? off + ES * static_cast<uint32_t>(32 * CH * k) : off;
+            if constexpr (U16) {
+                if constexpr (CH == 1) {
+                    typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+                    const u2 t = __builtin_amdgcn_raw_buffer_load_b64(rimg, o, 0, 0);
+                    raw[k][0] = t[0];
+                    raw[k][1] = t[1];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) raw[k][j] = __builtin_amdgcn_raw_buffer_load_b16(rimg, o + static_cast<uint32_t>(2 * CH * j), 0, 0);
+                }
+            } else if (CH == 1) {
                 const u4 t = __builtin_amdgcn_raw_buffer_load_b128(rimg, o, 0, 0);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) raw[k][j] = t[j];
@@ -202,7 +231,10 @@ __global__ __launch_bounds__(256, 1) void ff_blur_f32(const float* __restrict__ 
         uint32_t hp[2], lp[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const f2 vv = { __uint_as_float(raw[k][2 * j]) * scale, __uint_as_float(raw[k][2 * j + 1]) * scale };
+            f2 vv;
+            if constexpr (!U16) vv = f2{ __uint_as_float(raw[k][2 * j]) * scale, __uint_as_float(raw[k][2 * j + 1]) * scale };
+            else if constexpr (CH == 1) vv = f2{ static_cast<float>(raw[k][j] & 0xffffu) * scale, static_cast<float>(raw[k][j] >> 16) * scale };
+            else vv = f2{ static_cast<float>(raw[k][2 * j]) * scale, static_cast<float>(raw[k][2 * j + 1]) * scale };
             hp[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(vv, h2));
             float r0, r1;
             mx_remainder(hp[j], vv[0], vv[1], r0, r1);
@@ -286,20 +318,35 @@ __global__ __launch_bounds__(256, 1) void ff_blur_f32(const float* __restrict__ 
             fx_swap4(hp[4 * hf], hp[4 * hf + 2], hp[4 * hf + 1], hp[4 * hf + 3], lp[4 * hf], lp[4 * hf + 2], lp[4 * hf + 1], lp[4 * hf + 3]);
         }
     };
-    // E + F: rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column of the finished tile -> f32, stored at once.  Buffer stores: rows
-    // past the image, pixels right of it and tiles that do not exist get an offset outside the resource
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows) * g.cols * static_cast<uint32_t>(4 * CH), kMxRsrcWord3);
-    const uint32_t rowstep = 4u * static_cast<uint32_t>(g.cols) * CH;
+    // E + F: rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column of the finished tile -> f32 (u16: rounded), stored at once.  Buffer
+    // stores: rows past the image, pixels right of it and tiles that do not exist get an offset outside the resource
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows) * g.cols * static_cast<uint32_t>(ES * CH), kMxRsrcWord3);
+    const uint32_t rowstep = ES * static_cast<uint32_t>(g.cols) * CH;
     const int xcol = x0 + 32 * wave + m;
     auto emit_store = [&](int tile, bool valid, int gq) __attribute__((always_inline)) {
         const int row0 = 32 * tile + 8 * gq + 4 * h;
-        const uint32_t base = 4u * ((static_cast<uint32_t>(row0) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c));
+        const uint32_t base = ES * ((static_cast<uint32_t>(row0) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c));
+        if constexpr (U16) {
+            uint32_t u[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int reg = 4 * gq + k;
-            const float v = __builtin_fmaf(tfin[reg] * kMxUnscale, unscale, (reg & 1) ? cneg : cpos);
-            const bool ok = valid && xcol < g.cols && row0 + k < g.rows;
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, ok ? base + k * rowstep : 0xfffffff0u, 0, 0);
+            for (int k = 0; k < 4; ++k) {
+                const int reg = 4 * gq + k;
+                const float v = __builtin_fmaf(tfin[reg] * kMxUnscale, unscale, (reg & 1) ? cneg : cpos);
+                u[k] = static_cast<uint32_t>(static_cast<int>(v + 0.5f)) & 0xffffu;          // add 0.5, truncate, keep the low 16 bits
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool ok = valid && xcol < g.cols && row0 + k < g.rows;
+                __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(u[k]), rout, ok ? base + k * rowstep : 0xfffffff0u, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int reg = 4 * gq + k;
+                const float v = __builtin_fmaf(tfin[reg] * kMxUnscale, unscale, (reg & 1) ? cneg : cpos);
+                const bool ok = valid && xcol < g.cols && row0 + k < g.rows;
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, ok ? base + k * rowstep : 0xfffffff0u, 0, 0);
+            }
         }
     };
     auto colpass = [&](int qs, int hb, int ri, auto beside) __attribute__((always_inline)) {
@@ -385,44 +432,50 @@ __global__ __launch_bounds__(256, 1) void ff_blur_f32(const float* __restrict__ 
 // The classes that are instantiated: all but NKB = 23 with 3 or 4 channels, whose strided loads leave no registers for the window
 // (768 bytes of scratch per lane); those take the plane fallback
 __host__ __device__ constexpr bool ff_class_ok(int nkb, int ch) { return !(nkb >= 23 && ch != 1); }
+// u16: every class fits (NKB 23 with 3 / 4 channels: 256 VGPRs, 234 / 223 AGPRs, no scratch)
+template <typename T> __host__ __device__ constexpr bool ff_class_ok_t(int nkb, int ch)
+{
+    return std::is_same_v<T, uint16_t> || ff_class_ok(nkb, ch);
+}
 // The classes the library's own choice takes.  The f32 accumulation over 2 x 3 products per window block reaches 1.02e-6 (NKB 19)
 // and 1.11e-6 (NKB 21, 23) of max|x| where the output is as large as max|x| over an area (steps, constants), and 1.19e-6 at NKB 17
 // with max|x| = 0.7e30, past the contract's 1e-6; NKB <= 15 was measured within it (9.0e-7).  AUTO takes the plane fallback for pad
 // 105 .. 168; FUSED still runs the kernel.
 __host__ __device__ constexpr bool ff_class_in_contract(int nkb) { return nkb <= 15; }
 
-struct FfEntry {
+template <typename T> struct FfEntryT {
     int nkb;
-    // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (qk.mbits always is)
-    hipError_t (*blur_f32)(hipStream_t, const float* src, float* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk,
-                           const float* strips);
+    // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (float: qk.mbits always is; u16: never read)
+    hipError_t (*blur)(hipStream_t, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk, const T* strips);
 };
+using FfEntry = FfEntryT<float>;
+using FfEntryU16 = FfEntryT<uint16_t>;
 
-template <int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const float* src, float* dst, const void* frags, FxGeom g, int num_cus, const FfQuirk& qk,
-                                                   bool quirk, const float* strips)
+template <typename T, int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int num_cus, const FfQuirk& qk,
+                                                               bool quirk, const T* strips)
 {
     using C = FfCfg<NKB>;
     const FxLaunch l = fx_plan_launch(g, CH, C::NT, num_cus);
     if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
-    const hipError_t e = fx_set_lds(attr_done, C::LDS, ff_blur_f32<NKB, true, CH>, ff_blur_f32<NKB, false, CH>);
+    const hipError_t e = fx_set_lds(attr_done, C::LDS, ff_blur<T, NKB, true, CH>, ff_blur<T, NKB, false, CH>);
     if (e != hipSuccess) return e;
     if (quirk)
-        hipLaunchKernelGGL((ff_blur_f32<NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
+        hipLaunchKernelGGL((ff_blur<T, NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
                            l.nseg, static_cast<int>(l.ntasks), qk, strips);
     else
-        hipLaunchKernelGGL((ff_blur_f32<NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
+        hipLaunchKernelGGL((ff_blur<T, NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
                            l.nseg, static_cast<int>(l.ntasks), qk, strips);
     return hipGetLastError();
 }
 
-template <int NKB> hipError_t ff_launch_f32(hipStream_t st, const float* src, float* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk,
-                                            bool quirk, const float* strips)
+template <typename T, int NKB> hipError_t ff_launch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk,
+                                                    bool quirk, const T* strips)
 {
-    if (ch == 1) return ff_launch_ch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
-    if constexpr (ff_class_ok(NKB, 3)) {
-        if (ch == 3) return ff_launch_ch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
-        if (ch == 4) return ff_launch_ch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
+    if (ch == 1) return ff_launch_ch<T, NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
+    if constexpr (ff_class_ok_t<T>(NKB, 3)) {
+        if (ch == 3) return ff_launch_ch<T, NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
+        if (ch == 4) return ff_launch_ch<T, NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
     }
     return hipErrorInvalidValue;
 }
@@ -431,25 +484,35 @@ template <int NKB> hipError_t ff_launch_f32(hipStream_t st, const float* src, fl
     namespace blur_amd {                                                                                    \
     const FfEntry* ff_entry_##NKB_()                                                                        \
     {                                                                                                       \
-        static const FfEntry e = { NKB_, ff_launch_f32<NKB_> };                                             \
+        static const FfEntry e = { NKB_, ff_launch<float, NKB_> };                                          \
+        return &e;                                                                                          \
+    }                                                                                                       \
+    }
+
+// the u16 instantiations: translation units of their own (ff_u16_conv_<NKB>.hip)
+#define BLUR_FF_U16(NKB_)                                                                                   \
+    namespace blur_amd {                                                                                    \
+    const FfEntryU16* ff_u16_entry_##NKB_()                                                                 \
+    {                                                                                                       \
+        static const FfEntryU16 e = { NKB_, ff_launch<uint16_t, NKB_> };                                    \
         return &e;                                                                                          \
     }                                                                                                       \
     }
 
 // ---- what runs before the fused kernel (engine.hip) ------------------------------------------------------------------
-// strips[f][strip][row][CH (128 + 2 pada)] floats: the window of an edge chunk with the mirrored pixels in place.  A thread moves
-// one float.
-template <int CH>
-__device__ __forceinline__ void ff_edge_strips_body(const float* __restrict__ src, float* __restrict__ strips, int rows, int cols, int pada, int chunks,
+// strips[f][strip][row][CH (128 + 2 pada)] samples: the window of an edge chunk with the mirrored pixels in place.  A thread moves
+// one sample.
+template <typename T, int CH>
+__device__ __forceinline__ void ff_edge_strips_body(const T* __restrict__ src, T* __restrict__ strips, int rows, int cols, int pada, int chunks,
                                                     int nright, int bx, int sidx, int f)
 {
-    const int win = kFxChunk + 2 * pada, fpr = CH * win;                // floats per strip row
+    const int win = kFxChunk + 2 * pada, fpr = CH * win;                // samples per strip row
     const int nleft = fx_left_strips(pada);
     const int xc = sidx < nleft ? sidx : chunks - nright + sidx - nleft, x0 = kFxChunk * xc;
     const int i = bx * 256 + threadIdx.x;
     if (i >= rows * fpr) return;
     const int r = i / fpr, e = i - r * fpr, p = e / CH, ch = e - p * CH;
-    const float* line = src + (static_cast<size_t>(f) * rows + r) * cols * CH;
+    const T* line = src + (static_cast<size_t>(f) * rows + r) * cols * CH;
     strips[((static_cast<size_t>(f) * (nleft + nright) + sidx) * rows + r) * fpr + e] = line[CH * mx_refl(x0 - pada + p, cols) + ch];
 }
 
@@ -457,7 +520,7 @@ __device__ __forceinline__ void ff_edge_strips_body(const float* __restrict__ sr
 // 256 (CH = 1, 4) or 255 (CH = 3): element j BS + t of the batch belongs to thread t, so that all of a thread's elements are of
 // channel t mod CH.  Always: max|x| of the frame into mbits (integer atomicMax on the bits: order-free).  With `sums`: the parts of
 // Srow per batch (spart[f][batch][row][CH]) and the column sums per band (cpart), f32 products summed in double, every sum in a
-// fixed order.
+// fixed order.  u16 samples: no max (mbits is not touched); the sums hold integers below 2^53, exact in any order.
 constexpr int kFfSumRows = 16;
 __host__ __device__ constexpr int ff_batch_stride(int ch) { return ch == 3 ? 255 : 256; }
 inline int ff_groups_per_thread(int cols, int ch)
@@ -466,18 +529,22 @@ inline int ff_groups_per_thread(int cols, int ch)
     return ne <= bs ? 1 : (ne <= 2 * bs ? 2 : 4);
 }
 
-template <int CH, int G>
-__device__ __forceinline__ void ff_altsums_body(const float* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
+template <typename T, int CH, int G>
+__device__ __forceinline__ void ff_altsums_body(const T* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
                                                 int rows, int cols, int pad, int nbands, int nbatches, int cpitch, int band, int batch, int f, int band_rows, bool sums)
 {
     constexpr int BS = ff_batch_stride(CH);
+    constexpr bool U16 = std::is_same_v<T, uint16_t>;
+    if constexpr (U16) {
+        if (!sums) return;
+    }
     __shared__ double red[kFfSumRows][256];
     __shared__ double red2[kFfSumRows][16][CH];
     __shared__ float wmax[4];
     const int tid = threadIdx.x;
     const uint32_t ne = static_cast<uint32_t>(cols) * CH;
-    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src + static_cast<size_t>(f) * rows * ne), 0,
-                                                                          static_cast<uint32_t>(rows) * ne * 4u, kMxRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src + static_cast<size_t>(f) * rows * ne), 0,
+                                                                          static_cast<uint32_t>(rows) * ne * static_cast<uint32_t>(sizeof(T)), kMxRsrcWord3);
     const int r0 = band * band_rows, r1 = min(r0 + band_rows, rows);
     int dj[G], wx[G];
     bool own[G];
@@ -496,10 +563,14 @@ __device__ __forceinline__ void ff_altsums_body(const float* __restrict__ src, u
         for (int r = rs; r < re; ++r) {
             float v[G];
 #pragma unroll
-            for (int j = 0; j < G; ++j)
-                v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rimg, own[j] ? 4u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
+            for (int j = 0; j < G; ++j) {
+                if constexpr (U16) v[j] = static_cast<float>(__builtin_amdgcn_raw_buffer_load_b16(rimg, own[j] ? 2u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
+                else v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rimg, own[j] ? 4u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
+            }
+            if constexpr (!U16) {
 #pragma unroll
-            for (int j = 0; j < G; ++j) amax = fmaxf(amax, fabsf(v[j]));
+                for (int j = 0; j < G; ++j) amax = fmaxf(amax, fabsf(v[j]));
+            }
             if (sums) {
                 const int wy = mx_alt_weight(r, rows, pad);
                 double s = 0.0;
@@ -541,35 +612,37 @@ __device__ __forceinline__ void ff_altsums_body(const float* __restrict__ src, u
         for (int j = 0; j < G; ++j)
             if (own[j]) cpart[(static_cast<size_t>(f) * nbands + band) * cpitch + dj[j]] = col[j];
     }
-    // the workgroup's max|x| (NaN: the largest bits) -> one integer atomicMax
-    unsigned mb = __float_as_uint(amax);
+    if constexpr (!U16) {
+        // the workgroup's max|x| (NaN: the largest bits) -> one integer atomicMax
+        unsigned mb = __float_as_uint(amax);
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mb = max(mb, static_cast<unsigned>(__shfl_xor(static_cast<int>(mb), o)));
-    if ((tid & 63) == 0) wmax[tid >> 6] = __uint_as_float(mb);
-    __syncthreads();
-    if (tid == 0) {
-        unsigned m4 = 0;
+        for (int o = 32; o >= 1; o >>= 1) mb = max(mb, static_cast<unsigned>(__shfl_xor(static_cast<int>(mb), o)));
+        if ((tid & 63) == 0) wmax[tid >> 6] = __uint_as_float(mb);
+        __syncthreads();
+        if (tid == 0) {
+            unsigned m4 = 0;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) m4 = max(m4, __float_as_uint(wmax[w]));
-        atomicMax(mbits + f, m4);
+            for (int w = 0; w < 4; ++w) m4 = max(m4, __float_as_uint(wmax[w]));
+            atomicMax(mbits + f, m4);
+        }
     }
 }
 
 // One launch: the max and (with sums) the quirk's parts (n_alt = bands x batches x frames workgroups), then the edge strips
-// (strip_blocks x nstrips x frames workgroups).  mbits must be zero before the launch.
-template <int CH, int G>
-__global__ __launch_bounds__(256) void ff_prepass(const float* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
-                                                  float* __restrict__ strips, int rows, int cols, int pad, int pada, int nbands, int nbatches, int cpitch, int n_alt,
+// (strip_blocks x nstrips x frames workgroups).  Float: mbits must be zero before the launch; u16: mbits is not touched.
+template <typename T, int CH, int G>
+__global__ __launch_bounds__(256) void ff_prepass(const T* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
+                                                  T* __restrict__ strips, int rows, int cols, int pad, int pada, int nbands, int nbatches, int cpitch, int n_alt,
                                                   int chunks, int nright, int strip_blocks, int band_rows, int sums)
 {
     int b = blockIdx.x;
     if (b < n_alt) {
         const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
-        ff_altsums_body<CH, G>(src, mbits, spart, cpart, rows, cols, pad, nbands, nbatches, cpitch, band, batch, f, band_rows, sums != 0);
+        ff_altsums_body<T, CH, G>(src, mbits, spart, cpart, rows, cols, pad, nbands, nbatches, cpitch, band, batch, f, band_rows, sums != 0);
     } else {
         b -= n_alt;
         const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);
-        ff_edge_strips_body<CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f);
+        ff_edge_strips_body<T, CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f);
     }
 }
 

@@ -1,5 +1,5 @@
-// ff_registry.hpp -- the fused kernels for float32 images, one translation unit per window class of fx_registry.hpp
-// (ff_conv_<NKB>.hip).  A kernel serves every pad <= 8 (NKB - 2).
+// ff_registry.hpp -- the fused kernels for float32 and u16 images, one translation unit per pixel type and window class of
+// fx_registry.hpp (ff_conv_<NKB>.hip, ff_u16_conv_<NKB>.hip).  A kernel serves every pad <= 8 (NKB - 2).
 #pragma once
 #include "ff_kernels.hpp"
 #include "fx_registry.hpp"
@@ -13,6 +13,18 @@ inline const FfEntry* find_ff_entry(int nkb)
     static const FfEntry* const list[] = { BLUR_FX_CLASSES(BLUR_FF_ITEM) };
 #undef BLUR_FF_ITEM
     for (const FfEntry* e : list)
+        if (e->nkb == nkb) return e;
+    return nullptr;
+}
+#define BLUR_FF_DECL(NKB_) const FfEntryU16* ff_u16_entry_##NKB_();
+BLUR_FX_CLASSES(BLUR_FF_DECL)
+#undef BLUR_FF_DECL
+inline const FfEntryU16* find_ff_u16_entry(int nkb)
+{
+#define BLUR_FF_ITEM(NKB_) ff_u16_entry_##NKB_(),
+    static const FfEntryU16* const list[] = { BLUR_FX_CLASSES(BLUR_FF_ITEM) };
+#undef BLUR_FF_ITEM
+    for (const FfEntryU16* e : list)
         if (e->nkb == nkb) return e;
     return nullptr;
 }

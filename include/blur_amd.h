@@ -197,6 +197,37 @@ int blur_gaussian_f32_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int r
 int blur_gaussian_f32_host(blur_ctx* ctx, const float* src, float* dst, int rows, int cols, int channels, double sigma,
                            const blur_opts* opts);
 
+/* u16 frames (16-bit PNG / TIFF, camera RAW, depth maps: CV_16U) of 1, 3 or 4 channels, interleaved, rows*cols*channels samples
+   per frame, nframes back to back, DEVICE pointers (2-byte aligned; any element offset, so a pointer need not be 4-byte aligned).
+   Every channel is blurred on its own exactly as pffft_() blurs one of its planes (sizing and kernel from (rows, cols, sigma),
+   reflect-101, the Nyquist-slot quirk per channel plane unless opts->nyquist_quirk = 0).  With v the float plane (what
+   blur_gaussian_f32_* returns for the same frame widened to float) the output sample is
+       (uint16_t)((uint32_t)(int32_t)(v + 0.5f) & 0xffff)
+   the reference's interleave_BGR<T, U> rule (Utils.hpp:186-210) with T = uint16_t: add 0.5, truncate towards zero, keep the low 16
+   bits.  NO clamping: with the quirk on, full-scale content leaves the range on both sides and wraps (a constant 65535 frame can
+   come out as 250, a 0 / 65533 step as 65363), as u8 output wraps at 255.5.  The alpha channel is blurred like the others;
+   channels == 3 has no shortcut to a u8c3 path.  Parity: the sample equals the rule applied to the float64 reference plane,
+   except where that plane + 0.5 lies within 1e-6 * 65535 + 2^-9 = 0.0675 of an integer (the float entry's bound at full scale,
+   plus half a float32 ulp at 65535); there it may be one level off (modulo 65536).  opts->engine as for blur_gaussian_f32_*: AUTO
+   takes the fused matrix-core kernel for pad <= 104 (frames of at most 4 GiB - 4 KiB), the f32 plane path per channel
+   elsewhere; FUSED runs the fused kernel wherever one exists (pad <= 168, every channel count) and fails with
+   BLUR_ERR_UNSUPPORTED elsewhere: for pad 105 .. 168 it shares the float kernel's f32-accumulator rounding, outside the parity bound
+   where the output is near full scale over an area (steps, constants), which is why AUTO does not take it there; FFT always
+   takes the plane path; other engines are BLUR_ERR_UNSUPPORTED.  blur_last_engine reports 6 (fused) or 0 (plane path).  The call
+   is asynchronous on the context's stream.  Results are bit-reproducible: a frame gives the same bits alone and inside a batch
+   (the scale is a constant of the call, 2^e with 65535 B 2^e in [2^13, 2^14), not the frame's maximum; the quirk's sums are
+   integers held in doubles, exact in any order).  d_dst may equal d_src; other overlaps are detected over the whole batch and
+   read from a copy.  BLUR_ERR_INVALID: channels not in {1, 3, 4}, a NULL pointer, nframes < 0, rows, cols or sigma <= 0;
+   BLUR_ERR_UNSUPPORTED: pad > min(rows, cols) - 1.  These are checked before the device is touched (ctx may then be NULL);
+   nframes == 0 is a no-op. */
+int blur_gaussian_u16_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                double sigma, const blur_opts* opts);
+int blur_gaussian_u16_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, double sigma,
+                          const blur_opts* opts);
+/* the same for one frame in HOST memory: copy in, blur, copy out, synchronise */
+int blur_gaussian_u16_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, double sigma,
+                           const blur_opts* opts);
+
 /* HOST pointers: copy in, blur, copy out, synchronise (what a cv::Mat caller needs). */
 int blur_gaussian_u8c3_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst,
                             int rows, int cols, double sigma, const blur_opts* opts);
@@ -330,6 +361,11 @@ int blur_gaussian_u8_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t
 int blur_gaussian_f32_batch_multi_dev(blur_multi* m, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels,
                                       double sigma, const blur_opts* opts);
 int blur_gaussian_f32_batch_multi_host(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels,
+                                       double sigma, const blur_opts* opts);
+/* blur_gaussian_u16_batch_dev over a batch, sharded by frame exactly like the calls above */
+int blur_gaussian_u16_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                      double sigma, const blur_opts* opts);
+int blur_gaussian_u16_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
                                        double sigma, const blur_opts* opts);
 /* fastboxblur over a batch, sharded by frame exactly like the two calls above, in place (blur_fastboxblur_u8_batch_dev on
    each shard); arguments and errors as blur_fastboxblur_u8_batch_dev, nframes == 0 is a no-op, shards without frames idle. */

@@ -229,6 +229,14 @@ inline void gaussian_blur(float* data, int rows, int cols, int channels, double 
     check(ctx, blur_gaussian_f32_host(ctx, data, data, rows, cols, channels, sigma, opts), "gaussian_blur");
 }
 
+// gaussian_blur for u16 images of 1, 3 or 4 channels, in place: every channel blurred on its own as pffft_ blurs one of its
+// planes; (v + 0.5f) truncated, the low 16 bits kept, no clamping (blur_gaussian_u16_host)
+inline void gaussian_blur(uint16_t* data, int rows, int cols, int channels, double sigma, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u16_host(ctx, data, data, rows, cols, channels, sigma, opts), "gaussian_blur");
+}
+
 // pocketfft_1D(image, sigma) (Source.cpp:280-392) and pocketfft_2D(image, sigma) (Source.cpp:143-277): the two
 // pocketfft paths multiply all N/2+1 bins with the kernel's own spectrum (no Nyquist-slot quirk) and, inside the
 // cropped image, both equal the linear convolution of the reflect-101 extended image -- the engine's
