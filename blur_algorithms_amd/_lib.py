@@ -57,6 +57,12 @@ SYMBOLS = {
     "blur_gaussian_u16_batch_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
     "blur_gaussian_u16_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
     "blur_gaussian_u16_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_batch_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_batch_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
     "blur_gaussian_u8c3_host_pitched": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
     "blur_gaussian_f32c1_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
     "blur_separable_u8c3_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.POINTER(BlurOpts)]),
@@ -88,6 +94,10 @@ SYMBOLS = {
     "blur_gaussian_f32_batch_multi_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
     "blur_gaussian_u16_batch_multi_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
     "blur_gaussian_u16_batch_multi_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_batch_multi_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_batch_multi_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_batch_multi_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_batch_multi_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(BlurOpts)]),
     "blur_fastboxblur_u8_batch_multi_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "blur_fastboxblur_u8_batch_multi_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "blur_convolve_lines_c32_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),

@@ -121,9 +121,50 @@ def _gauss_frames_shape(shape):
 _gauss_f32_frames_shape = _gauss_frames_shape      # (the float32 entry points' name for the same helper)
 
 
+BF16 = "bfloat16"      # the dtype key of the bfloat16 entries (numpy has no bfloat16: host frames are CPU torch.bfloat16 tensors)
+
+
+def _dtype_name(dtype):
+    return dtype if isinstance(dtype, str) else np.dtype(dtype).name
+
+
+def _is_host_frames(image, dtype):
+    """whether a per-channel Gaussian call takes the host route: a numpy array, or for bfloat16 a CPU torch tensor"""
+    if isinstance(image, np.ndarray):
+        return True
+    return dtype == BF16 and not getattr(image, "is_cuda", True)
+
+
+def _bf16_bits(t, what):
+    """a contiguous CPU torch.bfloat16 tensor as a numpy uint16 array over the same memory"""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16 or t.is_cuda:
+        raise ValueError("%s: expected a torch.bfloat16 tensor" % what)
+    return t.contiguous().view(torch.uint16).numpy()
+
+
+def _gauss_result(res, out, dtype):
+    """what a host-route call returns: the result array; bfloat16: a CPU torch.bfloat16 tensor over it (or `out`)"""
+    if dtype != BF16:
+        return res
+    import torch
+    return out if out is not None else torch.from_numpy(res).view(torch.bfloat16)
+
+
 def _gauss_array(image, out, dtype, batch=False):
     """the host arrays of a per-channel Gaussian call: (source, result, (n, rows, cols, C)).  uint8 input of another dtype is
-    converted, as pffft_ does; float32 input must be float32 and uint16 input uint16.  batch: frames [n, rows, cols, C] only"""
+    converted, as pffft_ does; float32 input must be float32, uint16 input uint16 and float16 input float16; bfloat16 input is a
+    CPU torch.bfloat16 tensor, passed as its 16-bit patterns.  batch: frames [n, rows, cols, C] only"""
+    if dtype == BF16:
+        if isinstance(image, np.ndarray):
+            raise ValueError("expected a torch.bfloat16 tensor (numpy has no bfloat16; a uint16 array is a u16 image)")
+        image = _bf16_bits(image, "image")
+        if out is not None:
+            bits = _bf16_bits(out, "out")
+            if not out.is_contiguous() or bits.shape != image.shape:
+                raise ValueError("out must match the input")
+            out = bits
+        dtype = np.uint16
     if dtype != np.uint8 and image.dtype != dtype:
         raise ValueError("expected a %s array" % np.dtype(dtype).name)
     a = np.ascontiguousarray(image, dtype)
@@ -140,12 +181,12 @@ def _gauss_tensor(image, out, dtype, device=None):
     """the CUDA tensors of a per-channel Gaussian call: (source, result (default: the source), (n, rows, cols, C)).  device: frames
     [n, rows, cols, C] on that device only"""
     import torch
-    want = {np.uint8: torch.uint8, np.uint16: torch.uint16, np.float32: torch.float32}[dtype]
+    want = {np.uint8: torch.uint8, np.uint16: torch.uint16, np.float32: torch.float32, np.float16: torch.float16, BF16: torch.bfloat16}[dtype]
     t = image
     if (not isinstance(t, torch.Tensor) or t.dtype != want or not t.is_cuda or not t.is_contiguous()
             or (device is not None and (t.dim() != 4 or t.device.index != device))):
         layout = "[rows, cols], [rows, cols, C] or [n, rows, cols, C]" if device is None else "[n, rows, cols, C] on devices[0]"
-        raise ValueError("expected a contiguous CUDA %s tensor %s" % (np.dtype(dtype).name, layout))
+        raise ValueError("expected a contiguous CUDA %s tensor %s" % (_dtype_name(dtype), layout))
     shape = _gauss_frames_shape(tuple(t.shape))
     dst = t if out is None else out
     if not isinstance(dst, torch.Tensor) or dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
@@ -515,14 +556,37 @@ class BlurContext:
         return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.uint16, self._lib.blur_gaussian_u16_host,
                               self._lib.blur_gaussian_u16_batch_dev)
 
+    def gaussian_f16(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
+        """Gaussian blur of a float16 (IEEE binary16) image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows,
+        cols, C].  Every channel is blurred on its own as pffft_ blurs one of its planes; the float result is rounded once to
+        float16, to nearest even, values past 65504 to +-Inf (blur_gaussian_f16_batch_dev).  engine: None (the library's choice),
+        "fused" or "fft".
+
+        torch CUDA tensor (torch.float16): asynchronous on torch's current stream, returns `out` (default: in place).  numpy float16
+        array: host round trip, returns a new array.  A uint16 array is refused: it is a u16 image (gaussian_u16).
+        """
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.float16, self._lib.blur_gaussian_f16_host,
+                              self._lib.blur_gaussian_f16_batch_dev)
+
+    def gaussian_bf16(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
+        """Gaussian blur of a bfloat16 image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows, cols, C].  Every
+        channel is blurred on its own as pffft_ blurs one of its planes; the float result is rounded once to bfloat16, to nearest
+        even (blur_gaussian_bf16_batch_dev).  engine: None (the library's choice), "fused" or "fft".
+
+        torch CUDA tensor (torch.bfloat16): asynchronous on torch's current stream, returns `out` (default: in place).  CPU
+        torch.bfloat16 tensor: host round trip, returns a new CPU tensor (numpy has no bfloat16; a numpy array is refused).
+        """
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, BF16, self._lib.blur_gaussian_bf16_host,
+                              self._lib.blur_gaussian_bf16_batch_dev)
+
     def _gaussian(self, image, sigma, out, nyquist_quirk, engine, dtype, host_entry, batch_dev_entry):
         o = self._opts(nyquist_quirk, engine=engine)
-        if isinstance(image, np.ndarray):
+        if _is_host_frames(image, dtype):
             a, res, (n, rows, cols, ch) = _gauss_array(image, out, dtype)
             fb = rows * cols * ch * a.itemsize
             for f in range(n):
                 self._check(host_entry(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch, float(sigma), C.byref(o)))
-            return res
+            return _gauss_result(res, out, dtype)
         t, dst, (n, rows, cols, ch) = _gauss_tensor(image, out, dtype)
         self.use_torch_stream()
         self._check(batch_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
@@ -631,16 +695,28 @@ class BlurMulti:
         return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.uint16, self._lib.blur_gaussian_u16_batch_multi_host,
                               self._lib.blur_gaussian_u16_batch_multi_dev)
 
+    def gaussian_f16(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
+        """BlurContext.gaussian_f16 over a batch sharded by frame: frames float16 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
+        tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.float16, self._lib.blur_gaussian_f16_batch_multi_host,
+                              self._lib.blur_gaussian_f16_batch_multi_dev)
+
+    def gaussian_bf16(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
+        """BlurContext.gaussian_bf16 over a batch sharded by frame: frames torch.bfloat16 [n, rows, cols, C], C in {1, 3, 4}; a CUDA
+        tensor on devices[0] (default: in place) or a CPU tensor (a new CPU tensor).  Synchronous."""
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, BF16, self._lib.blur_gaussian_bf16_batch_multi_host,
+                              self._lib.blur_gaussian_bf16_batch_multi_dev)
+
     def _gaussian(self, frames, sigma, out, nyquist_quirk, engine, dtype, multi_host_entry, multi_dev_entry):
         o = BlurOpts()
         self._lib.blur_opts_default(C.byref(o))
         o.nyquist_quirk = 1 if nyquist_quirk else 0
         if engine is not None:
             o.engine = ENGINES[engine]
-        if isinstance(frames, np.ndarray):
+        if _is_host_frames(frames, dtype):
             a, res, (n, rows, cols, ch) = _gauss_array(frames, out, dtype, batch=True)
             self._check(multi_host_entry(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, float(sigma), C.byref(o)))
-            return res
+            return _gauss_result(res, out, dtype)
         import torch
         t, dst, (n, rows, cols, ch) = _gauss_tensor(frames, out, dtype, device=self.devices[0])
         torch.cuda.synchronize(t.device)

@@ -768,9 +768,9 @@ struct blur_ctx {
     size_t ch_planes_bytes = 0;
     uint8_t* ch_copy = nullptr;      // 1- / 4-channel images: a copy of overlapping source frames
     size_t ch_copy_bytes = 0;
-    void* ff_sums = nullptr;         // float32 / u16 images, fused kernel: max|x| per frame (float) and the quirk's sums (run_ff)
+    void* ff_sums = nullptr;         // float32 / u16 / half images, fused kernel: max|x| per frame (not u16) and the quirk's sums (run_ff)
     size_t ff_sums_bytes = 0;
-    void* ff_strips = nullptr;       // float32 / u16 images, fused kernel: the edge chunks' windows (samples of the frame's type)
+    void* ff_strips = nullptr;       // float32 / u16 / half images, fused kernel: the edge chunks' windows (samples of the frame's type)
     size_t ff_strips_bytes = 0;
     size_t box_bytes = 0;
     std::string engine_note;      // BLUR_ENGINE_AUTO: why the last call's choice passed over a faster engine ("" if it did not)
@@ -1699,11 +1699,28 @@ static int run_colpass_u8c3(blur_ctx* ctx, const float* planes, uint8_t* dst, in
 }
 
 // ======================================================================================
-// 1- and 4-channel u8 images (blur_gaussian_u8_*), float32 and u16 images of 1, 3 or 4 channels (blur_gaussian_f32_*,
-// blur_gaussian_u16_*): every channel blurred on its own as pffft_() blurs one of its planes (u8 and u16 with the + 0.5f truncation,
-// float32 without)
+// 1- and 4-channel u8 images (blur_gaussian_u8_*), float32, u16, float16 and bfloat16 images of 1, 3 or 4 channels
+// (blur_gaussian_f32_*, blur_gaussian_u16_*, blur_gaussian_f16_*, blur_gaussian_bf16_*): every channel blurred on its own as pffft_()
+// blurs one of its planes (u8 and u16 with the + 0.5f truncation, float32 without, the half types rounded once to nearest even)
 // ======================================================================================
 #include "ff_registry.hpp"
+
+// the per-channel entries' pixel types by name (messages), and the fused kernel of a window class by type
+template <typename T> constexpr const char* ch_type_name()
+{
+    if constexpr (std::is_same_v<T, uint16_t>) return "u16";
+    else if constexpr (std::is_same_v<T, ff_f16>) return "float16";
+    else if constexpr (std::is_same_v<T, ff_bf16>) return "bfloat16";
+    else if constexpr (std::is_same_v<T, float>) return "float32";
+    else return "u8";
+}
+template <typename T> static const FfEntryT<T>* find_ff_entry_t(int nkb)
+{
+    if constexpr (std::is_same_v<T, uint16_t>) return find_ff_u16_entry(nkb);
+    else if constexpr (std::is_same_v<T, ff_f16>) return find_ff_f16_entry(nkb);
+    else if constexpr (std::is_same_v<T, ff_bf16>) return find_ff_bf16_entry(nkb);
+    else return find_ff_entry(nkb);
+}
 
 static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
 {
@@ -1775,18 +1792,16 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
 // the fused kernel (ff_kernels.hpp): the pre-pass (max|x|, the quirk's sums, the edge chunks' strips), the quirk's finalisation,
 // then the kernel.  Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).  Every
 // partition of a sum (bands, batches) depends on the frame's shape only: a frame gives the same bits alone and in a batch.
-// T = float or uint16_t.  u16: no max|x| (the scale is a constant of the call), and without the quirk no sums at all.
+// T = float, uint16_t, ff_f16 or ff_bf16.  u16: no max|x| (the scale is a constant of the call), and without the quirk no sums at
+// all; the half types: as float.
 template <typename T>
 static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
 {
     constexpr bool u16 = std::is_same_v<T, uint16_t>;
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
-    const FfEntryT<T>* fe = nullptr;
-    if constexpr (u16) fe = find_ff_u16_entry(nkb);
-    else fe = find_ff_entry(nkb);
+    const FfEntryT<T>* fe = find_ff_entry_t<T>(nkb);
     if (!fe || !ff_class_ok_t<T>(nkb, ch))
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, u16 ? "fused kernel for u16 images: no kernel instantiated for this pad and channel count"
-                                                   : "fused kernel for float32 images: no kernel instantiated for this pad and channel count");
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, (std::string("fused kernel for ") + ch_type_name<T>() + " images: no kernel instantiated for this pad and channel count").c_str());
     FxGeom g{ rows, cols, p.sz.pad, nframes, 0, (rows + 31) / 32, fx_right_strips(cols, pada), ctx->num_xcds };
     const int chunks_x = (cols + kFxChunk - 1) / kFxChunk, win = kFxChunk + 2 * pada, nstrips = fx_left_strips(pada) + g.nright;
     if (int rc = ensure_buf(ctx, &ctx->ff_strips, &ctx->ff_strips_bytes,
@@ -1850,12 +1865,20 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
 // Float frames are scaled by a power of two on the way in and back on the way out (exact), as the fused kernel scales its frames:
 // the plane path's transforms are unnormalised f32, so max|x| near 1e37 overflowed in them and max|x| near 1e-37 lost bits to
 // subnormals.  mbits: the bits of max|x| over the frame (an integer atomicMax: the same result in any order); the scale puts
-// max|x| into [0.5, 1).  u8 and u16 frames are not scaled (mbits is not read).
-__global__ void chan_maxabs(const float* __restrict__ src, unsigned* __restrict__ mbits, size_t n)
+// max|x| into [0.5, 1).  u8 and u16 frames are not scaled (mbits is not read).  float16 / bfloat16 frames are widened to f32 (exact)
+// and then treated as float frames; chan_pack rounds the result once to nearest even, as the fused kernel does.
+template <typename T> __device__ __forceinline__ float chan_widen(T v)
+{
+    if constexpr (ff_is_half_v<T>) return ff_half_widen<T>(v.bits);
+    else return static_cast<float>(v);
+}
+
+template <typename T>
+__global__ void chan_maxabs(const T* __restrict__ src, unsigned* __restrict__ mbits, size_t n)
 {
     unsigned m = 0;
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        m = max(m, __float_as_uint(src[i]) & 0x7fffffffu);
+        m = max(m, __float_as_uint(chan_widen(src[i])) & 0x7fffffffu);
     if (m) atomicMax(mbits, m);
 }
 
@@ -1872,10 +1895,11 @@ template <typename T>
 __global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes, size_t px, int ch, const unsigned* __restrict__ mbits)
 {
     float scale = 1.f;
-    if constexpr (std::is_same_v<T, float>) scale = ldexpf(1.f, chan_scale_exp(*mbits));
+    if constexpr (std::is_same_v<T, float> || ff_is_half_v<T>) scale = ldexpf(1.f, chan_scale_exp(*mbits));
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
         for (int c = 0; c < ch; ++c) {
             if constexpr (std::is_same_v<T, float>) planes[c * px + i] = src[i * ch + c] * scale;
+            else if constexpr (ff_is_half_v<T>) planes[c * px + i] = chan_widen(src[i * ch + c]) * scale;
             else planes[c * px + i] = static_cast<float>(src[i * ch + c]);
         }
 }
@@ -1884,13 +1908,15 @@ template <typename T>
 __global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst, size_t px, int ch, const unsigned* __restrict__ mbits)
 {
     float unscale = 1.f;
-    if constexpr (std::is_same_v<T, float>) unscale = ldexpf(1.f, -chan_scale_exp(*mbits));
+    if constexpr (std::is_same_v<T, float> || ff_is_half_v<T>) unscale = ldexpf(1.f, -chan_scale_exp(*mbits));
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
         for (int c = 0; c < ch; ++c) {
             if constexpr (std::is_same_v<T, uint8_t>)  // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
                 dst[i * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffu);
             else if constexpr (std::is_same_v<T, uint16_t>)  // the same rule 16 bits wide: truncate, keep the low 16 bits
                 dst[i * ch + c] = static_cast<uint16_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffffu);
+            else if constexpr (ff_is_half_v<T>)             // one rounding to nearest even (binary16: overflow to +-Inf)
+                dst[i * ch + c] = T{ ff_half_round<T>(planes[c * px + i] * unscale) };
             else
                 dst[i * ch + c] = planes[c * px + i] * unscale;
         }
@@ -1909,9 +1935,9 @@ static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int 
     for (int f = 0; f < nframes; ++f) {
         const T* s = d_src + static_cast<size_t>(f) * px * ch;
         T* d = d_dst + static_cast<size_t>(f) * px * ch;
-        if constexpr (std::is_same_v<T, float>) {
+        if constexpr (std::is_same_v<T, float> || ff_is_half_v<T>) {
             HIP_TRY(ctx, hipMemsetAsync(mbits, 0, sizeof(unsigned), ctx->stream));
-            hipLaunchKernelGGL(chan_maxabs, dim3(blocks), dim3(256), 0, ctx->stream, s, mbits, px * ch);
+            hipLaunchKernelGGL(chan_maxabs<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, mbits, px * ch);
             HIP_TRY(ctx, hipGetLastError());
         }
         hipLaunchKernelGGL(chan_split<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch, mbits);
@@ -1927,7 +1953,7 @@ static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int 
     return BLUR_OK;
 }
 
-// the arguments of every blur_gaussian_{u8,f32,u16}_* entry, without the device (ctx may be NULL here: the status is the same)
+// the arguments of every blur_gaussian_{u8,f32,u16,f16,bf16}_* entry, without the device (ctx may be NULL here: the status is the same)
 static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nframes, int rows, int cols, int channels, double sigma)
 {
     if (channels != 1 && channels != 3 && channels != 4) return fail(ctx, BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
@@ -1939,22 +1965,23 @@ static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nf
     return ctx ? BLUR_OK : BLUR_ERR_INVALID;
 }
 
-// One driver for the three element types.  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused
+// One driver for the five element types (float16 and bfloat16: in everything below as float32, two bytes per sample).  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused
 // kernel for NKB 23 with 3 or 4 channels (ff_class_ok_t); the own choice of float32 and u16 stops at NKB 15 (ff_class_in_contract: at 16 bits
 // 1e-6 of full scale is 0.066 of a grey level); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 / run_ff<T>)
 // and the engine error's text
 template <typename T>
 static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
 {
-    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, ffk = !u8;      // ffk: the ff_kernels.hpp types
+    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;      // ffk: the ff_kernels.hpp types
     if (int rc = check_ch_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma)) return rc;
     if constexpr (u8) {
         if (channels == 3) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
     }
     const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
     if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, u16 ? "u16 images: engine must be AUTO, FUSED or FFT"
-                                                   : (ffk ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT"));
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, half ? (std::string(ch_type_name<T>()) + " images: engine must be AUTO, FUSED or FFT").c_str()
+                                                    : (u16 ? "u16 images: engine must be AUTO, FUSED or FFT"
+                                                           : (ffk ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT")));
     // The fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED: a kernel for the pad, the frame and quirk limits; a
     // float32 class instantiated for the channel count; the frame's bytes within 32-bit offsets), the plane fallback elsewhere.  AUTO
     // too: where the u8c3 policy passes the fused engine over for a compile-time FFT family (frames under 1 MP, pad > 152 on 6 MP), the
@@ -1976,7 +2003,8 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
         const char* why = nullptr;
         if (p.fx && ffk && !ff_class_ok_t<T>(p.fx->nkb, channels)) why = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
         else if (p.fx && ffk && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(p.fx->nkb))
-            why = u16 ? "fused kernel for u16 images: pad 105 .. 168 exceeds 1e-6 of full scale on full-scale content (1.2e-6); ask for it with engine = FUSED"
+            why = half ? "fused kernel for float16 / bfloat16 images: pad 105 .. 168 is outside the library's own choice, as for float32; ask for it with engine = FUSED"
+                  : u16 ? "fused kernel for u16 images: pad 105 .. 168 exceeds 1e-6 of full scale on full-scale content (1.2e-6); ask for it with engine = FUSED"
                       : "fused kernel for float32 images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED";
         else if (p.fx && static_cast<long long>(rows) * cols * channels * static_cast<long long>(sizeof(T)) > 0xfffff000ll)
             why = "fused matrix-core engine: frame too large for 32-bit offsets";
@@ -2025,7 +2053,7 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
     return BLUR_OK;
 }
 
-// blur_gaussian_{u8,f32,u16}_host: one frame through the context's host staging buffer (source and destination apart: no in-place copy)
+// blur_gaussian_{u8,f32,u16,f16,bf16}_host: one frame through the context's host staging buffer (source and destination apart: no in-place copy)
 template <typename T>
 static int blur_ch_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
 {
@@ -3354,7 +3382,7 @@ int blur_fastboxblur_u8_batch_multi_host(blur_multi* m, uint8_t* inout, int nfra
     return box_multi(m, inout, nframes, w, h, channels, ksize, passes, 0);
 }
 
-// blur_gaussian_{u8,f32,u16}_batch_multi_*: the frames of a batch sharded over the devices (a template: C++ linkage)
+// blur_gaussian_{u8,f32,u16,f16,bf16}_batch_multi_*: the frames of a batch sharded over the devices (a template: C++ linkage)
 extern "C++" {
 template <typename T>
 static int blur_ch_multi(blur_multi* m, const T* src, T* dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts, int location)
@@ -3458,6 +3486,64 @@ int blur_gaussian_u16_batch_multi_host(blur_multi* m, const uint16_t* src, uint1
                                        const blur_opts* opts)
 {
     return blur_ch_multi(m, src, dst, nframes, rows, cols, channels, sigma, opts, 0);
+}
+
+// float16 images of 1, 3 or 4 channels: the bit patterns in uint16_t (the C header has no 16-bit floating type)
+int blur_gaussian_f16_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                const blur_opts* opts)
+{
+    return blur_ch_batch_impl(ctx, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), nframes, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_f16_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_ch_batch_impl(ctx, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), 1, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_f16_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_ch_host(ctx, reinterpret_cast<const ff_f16*>(src), reinterpret_cast<ff_f16*>(dst), rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_f16_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                      const blur_opts* opts)
+{
+    return blur_ch_multi(m, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), nframes, rows, cols, channels, sigma, opts, 1);
+}
+
+int blur_gaussian_f16_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels, double sigma,
+                                       const blur_opts* opts)
+{
+    return blur_ch_multi(m, reinterpret_cast<const ff_f16*>(src), reinterpret_cast<ff_f16*>(dst), nframes, rows, cols, channels, sigma, opts, 0);
+}
+
+// bfloat16 images of 1, 3 or 4 channels: the bit patterns in uint16_t (the C header has no 16-bit floating type)
+int blur_gaussian_bf16_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                const blur_opts* opts)
+{
+    return blur_ch_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_bf16_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_ch_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), 1, rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_bf16_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    return blur_ch_host(ctx, reinterpret_cast<const ff_bf16*>(src), reinterpret_cast<ff_bf16*>(dst), rows, cols, channels, sigma, opts);
+}
+
+int blur_gaussian_bf16_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, double sigma,
+                                      const blur_opts* opts)
+{
+    return blur_ch_multi(m, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigma, opts, 1);
+}
+
+int blur_gaussian_bf16_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels, double sigma,
+                                       const blur_opts* opts)
+{
+    return blur_ch_multi(m, reinterpret_cast<const ff_bf16*>(src), reinterpret_cast<ff_bf16*>(dst), nframes, rows, cols, channels, sigma, opts, 0);
 }
 
 int blur_convolve_lines_c32_dev(blur_ctx* ctx, const float* d_in, float* d_out, int nlines, int n, const float* multipliers)

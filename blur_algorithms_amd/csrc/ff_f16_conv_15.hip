@@ -1,0 +1,3 @@
+// fused matrix-core kernel for float16 images of 1, 3 or 4 channels, 15 window blocks of 16 positions: pad <= 104; one channel per workgroup
+#include "ff_kernels.hpp"
+BLUR_FF_F16(15)

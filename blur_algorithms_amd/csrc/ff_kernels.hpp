@@ -1,4 +1,4 @@
-// ff_kernels.hpp -- the fused matrix-core kernel for float32 and u16 images of 1, 3 or 4 channels, every window class (NKB = 3 .. 23
+// ff_kernels.hpp -- the fused matrix-core kernel for float32, u16, float16 and bfloat16 images of 1, 3 or 4 channels, every window class (NKB = 3 .. 23
 // blocks of 16 positions: pad <= 168).
 //
 // The structure is fw_kernels.hpp's: a workgroup handles ONE channel of a strip of 128 pixel columns (channel fastest in the task
@@ -31,6 +31,16 @@
 //     stores after a lane-pair exchange were measured 4 % slower than the shorts: DESIGN.md section 2.3);
 //   * the quirk's sums: the same code as for floats.  Every term is an integer below 2^53 in a double (|Z| <= 4 x 65535 rows cols,
 //     and a frame's bytes fit 32 bits), so every sum is exact and the same in any order; no limit beyond the frame limit follows.
+//
+// T = ff_f16 (IEEE binary16) or ff_bf16 (bfloat16): blur_gaussian_f16_* / blur_gaussian_bf16_*.  The storage is 16 bits, so the loads,
+// stores and strips are the u16 instantiation's; the range comes from the content, so the scale and the pre-pass are the float
+// instantiation's (max|x| on the widened sample).  What is the half types' own:
+//   * staging: a binary16 sample times 2^e is a binary16 value, and a bfloat16 sample (8 significant bits) times 2^e fits
+//     binary16's 11: x s = hi, lo = 0.  ONE binary16 plane per window buffer (FfCfg<NKB, 1>), no remainder.  Only |x s| < 2^-14
+//     (a sample more than 2^27 / B below the frame's maximum) rounds, to a binary16 subnormal: at most 2^-25 in scaled units;
+//   * row pass: x_hi t_hi + x_hi t_lo, two products per window block (what the u8 kernels do);
+//   * emission: the float result v rounded ONCE to the sample type, to nearest even: binary16 by v_cvt_f16_f32 (|v| past 65504 gives
+//     +-Inf), bfloat16 by the conversion of float to __bf16 (v_cvt_pk_bf16_f32 on gfx950).  No + 0.5, no clamping.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -67,12 +77,32 @@ struct FfQuirk {
 
 constexpr float kFfRowUnscale = 1.f / 16384.f;      // V = acc 2^-14 (the taps' scaling)
 
-template <int NKB> struct FfCfg {
+// the pixel types of 16-bit floating-point frames: tags over the bit pattern (uint16_t is the u16 instantiation's)
+struct ff_f16 { uint16_t bits; };
+struct ff_bf16 { uint16_t bits; };
+template <typename T> inline constexpr bool ff_is_half_v = std::is_same_v<T, ff_f16> || std::is_same_v<T, ff_bf16>;
+template <typename T> inline constexpr bool ff_is_pixel_v = std::is_same_v<T, float> || std::is_same_v<T, uint16_t> || ff_is_half_v<T>;
+
+// a half-type sample (its bits in the low 16 of `bits`) as f32: exact for both types
+template <typename T> __device__ __forceinline__ float ff_half_widen(uint32_t bits)
+{
+    if constexpr (std::is_same_v<T, ff_f16>) return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(bits)));
+    else return __uint_as_float(bits << 16);
+}
+// f32 -> the half type, one rounding to nearest even (binary16: overflow to +-Inf, subnormals kept)
+template <typename T> __device__ __forceinline__ uint16_t ff_half_round(float v)
+{
+    if constexpr (std::is_same_v<T, ff_f16>) return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v));
+    else return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v));
+}
+
+// NP: binary16 planes per window buffer (2: hi and lo; 1: the half types, whose staged samples have no lo)
+template <int NKB, int NP = 2> struct FfCfg {
     using W = FwCfg<NKB>;
     static constexpr int PADA = W::PADA, WIN = W::WIN, GPR = W::GPR, PER = W::PER, PW = W::PW, NT = W::NT;
     static constexpr int BUF = W::BUF;                                // one binary16 plane of one window
-    // window buffer b, plane p (0 hi, 1 lo) at (2 b + p) BUF
-    static constexpr int TLOFF = 4 * BUF;
+    // window buffer b, plane p (0 hi, 1 lo) at (NP b + p) BUF
+    static constexpr int TLOFF = 2 * NP * BUF;
     static constexpr int QOFF = TLOFF + NKB * 64 * 16;
     static constexpr int LDS = QOFF + 2 * 2 * 32 * 4;
     static_assert(LDS <= 160 * 1024, "the LDS of one CU");
@@ -122,10 +152,11 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
                                                   int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips)
 {
     static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
-    static_assert(std::is_same_v<T, float> || std::is_same_v<T, uint16_t>, "float32 or u16 pixels");
-    constexpr bool U16 = std::is_same_v<T, uint16_t>;
+    static_assert(ff_is_pixel_v<T>, "float32, u16, float16 or bfloat16 pixels");
+    constexpr bool U16 = std::is_same_v<T, uint16_t>, HALF = ff_is_half_v<T>, W16 = U16 || HALF;      // W16: 16-bit storage
     constexpr uint32_t ES = sizeof(T);                              // bytes per sample
-    using C = FfCfg<NKB>;
+    constexpr int NP = HALF ? 1 : 2;                                // binary16 planes per window buffer
+    using C = FfCfg<NKB, NP>;
     constexpr int PADA = C::PADA, PW = C::PW, NT = C::NT, PER = C::PER;
     constexpr int RS = NKB;                                        // row-pass slots
     constexpr int CS = NKB > 9 ? NKB : 9;                         // column-pass slots: hand-off 0 .. 7, emission 1 .. 4, staging from 5
@@ -189,7 +220,7 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
     const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wbase), 0, wbytes, kMxRsrcWord3);
     const int srow = 8 * (tid >> 6) + ((tid >> 4) & 3) + 4 * ((tid >> 3) & 1), g0 = tid & 7;      // (fx_kernels.hpp: the staging map)
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    constexpr int NR = U16 && CH == 1 ? 2 : 4;                     // u16, 1 channel: a group's 4 samples in 2 registers
+    constexpr int NR = W16 && CH == 1 ? 2 : 4;                     // 16-bit samples, 1 channel: a group's 4 samples in 2 registers
     uint32_t raw[PER][NR];
     double qv = 0.0;
     // the window of step s: thread t moves channel c of the groups of 4 pixels g0 + 8 k of row srow, all requested at once
@@ -200,7 +231,7 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
         for (int k = 0; k < PER; ++k) {
             const bool in = (C::GPR % 8 == 0) || k < PER - 1 || g0 < C::GPR % 8;
             const uint32_t o = in ? off + ES * static_cast<uint32_t>(32 * CH * k) : off;
-            if constexpr (U16) {
+            if constexpr (W16) {
                 if constexpr (CH == 1) {
                     typedef uint32_t u2 __attribute__((ext_vector_type(2)));
                     const u2 t = __builtin_amdgcn_raw_buffer_load_b64(rimg, o, 0, 0);
@@ -222,27 +253,39 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
         if (QUIRK)              // the row term of row re of V (= image row refl(re - PADA)); every thread (row tid & 31: eight copies of each value)
             qv = qk.srow[(static_cast<size_t>(f) * g.rows + mx_refl(min(32 * s + (tid & 31), qrows - 1) - PADA, g.rows)) * CH + c];
     };
-    // group k: x s -> hi + lo binary16 -> the two planes in LDS (one ds_write_b64 each)
+    // group k: x s -> hi + lo binary16 -> the two planes in LDS (one ds_write_b64 each); the half types: x s = hi, one plane
     auto commit_item = [&](int buf, int k) __attribute__((always_inline)) {
         if (k >= PER) return;
-        _Float16* base = reinterpret_cast<_Float16*>(ff_lds + 2 * buf * C::BUF) + srow * PW + 4 * g0 + 32 * k;
+        _Float16* base = reinterpret_cast<_Float16*>(ff_lds + NP * buf * C::BUF) + srow * PW + 4 * g0 + 32 * k;
         typedef float f2 __attribute__((ext_vector_type(2)));
         typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        uint32_t hp[2], lp[2];
+        if constexpr (HALF) {
+            uint32_t hp[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            f2 vv;
-            if constexpr (!U16) vv = f2{ __uint_as_float(raw[k][2 * j]) * scale, __uint_as_float(raw[k][2 * j + 1]) * scale };
-            else if constexpr (CH == 1) vv = f2{ static_cast<float>(raw[k][j] & 0xffffu) * scale, static_cast<float>(raw[k][j] >> 16) * scale };
-            else vv = f2{ static_cast<float>(raw[k][2 * j]) * scale, static_cast<float>(raw[k][2 * j + 1]) * scale };
-            hp[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(vv, h2));
-            float r0, r1;
-            mx_remainder(hp[j], vv[0], vv[1], r0, r1);
-            const f2 rem = { r0, r1 };
-            lp[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(rem, h2));
+            for (int j = 0; j < 2; ++j) {
+                f2 vv;
+                if constexpr (CH == 1) vv = f2{ ff_half_widen<T>(raw[k][j] & 0xffffu) * scale, ff_half_widen<T>(raw[k][j] >> 16) * scale };
+                else vv = f2{ ff_half_widen<T>(raw[k][2 * j]) * scale, ff_half_widen<T>(raw[k][2 * j + 1]) * scale };
+                hp[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(vv, h2));
+            }
+            *reinterpret_cast<uint2*>(base) = make_uint2(hp[0], hp[1]);
+        } else {
+            uint32_t hp[2], lp[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                f2 vv;
+                if constexpr (!U16) vv = f2{ __uint_as_float(raw[k][2 * j]) * scale, __uint_as_float(raw[k][2 * j + 1]) * scale };
+                else if constexpr (CH == 1) vv = f2{ static_cast<float>(raw[k][j] & 0xffffu) * scale, static_cast<float>(raw[k][j] >> 16) * scale };
+                else vv = f2{ static_cast<float>(raw[k][2 * j]) * scale, static_cast<float>(raw[k][2 * j + 1]) * scale };
+                hp[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(vv, h2));
+                float r0, r1;
+                mx_remainder(hp[j], vv[0], vv[1], r0, r1);
+                const f2 rem = { r0, r1 };
+                lp[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(rem, h2));
+            }
+            *reinterpret_cast<uint2*>(base) = make_uint2(hp[0], hp[1]);
+            *reinterpret_cast<uint2*>(base + C::BUF / 2) = make_uint2(lp[0], lp[1]);
         }
-        *reinterpret_cast<uint2*>(base) = make_uint2(hp[0], hp[1]);
-        *reinterpret_cast<uint2*>(base + C::BUF / 2) = make_uint2(lp[0], lp[1]);
     };
     auto commit_q = [&](int buf) __attribute__((always_inline)) {
         if (QUIRK) {
@@ -254,14 +297,14 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
     };
     // R: the window in buffer `buf` -> arow; `beside(kb)` runs after the products of slot kb
     auto rowpass = [&](int buf, auto beside) __attribute__((always_inline)) {
-        const _Float16* base = reinterpret_cast<const _Float16*>(ff_lds + 2 * buf * C::BUF) + m * PW + wave * 32 + 8 * h;
-        const _Float16* lbase = base + C::BUF / 2;
+        const _Float16* base = reinterpret_cast<const _Float16*>(ff_lds + NP * buf * C::BUF) + m * PW + wave * 32 + 8 * h;
+        const _Float16* lbase = base + C::BUF / 2;                // (the half types have no lo plane: not read)
         mx_float16 a = zero;
         mx_half8 x[3], xl[3], tq[3];
 #pragma unroll
         for (int kb = 0; kb < 2 && kb < NKB; ++kb) {
             x[kb] = *reinterpret_cast<const mx_half8*>(base + 16 * kb);
-            xl[kb] = *reinterpret_cast<const mx_half8*>(lbase + 16 * kb);
+            if constexpr (!HALF) xl[kb] = *reinterpret_cast<const mx_half8*>(lbase + 16 * kb);
         }
         tq[0] = tlo(0);
         tq[1] = tlo(1);
@@ -269,12 +312,12 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
         for (int kb = 0; kb < RS; ++kb) {
             if (kb + 2 < NKB) {
                 x[(kb + 2) % 3] = *reinterpret_cast<const mx_half8*>(base + 16 * (kb + 2));
-                xl[(kb + 2) % 3] = *reinterpret_cast<const mx_half8*>(lbase + 16 * (kb + 2));
+                if constexpr (!HALF) xl[(kb + 2) % 3] = *reinterpret_cast<const mx_half8*>(lbase + 16 * (kb + 2));
                 tq[(kb + 2) % 3] = tlo(kb + 2);
             }
             a = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[kb % 3], th[kb], a, 0, 0, 0);
             a = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[kb % 3], tq[kb % 3], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl[kb % 3], th[kb], a, 0, 0, 0);
+            if constexpr (!HALF) a = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl[kb % 3], th[kb], a, 0, 0, 0);
             asm volatile("" : "+a"(a));
             beside(kb);
             __builtin_amdgcn_sched_barrier(0);
@@ -318,7 +361,7 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
             fx_swap4(hp[4 * hf], hp[4 * hf + 2], hp[4 * hf + 1], hp[4 * hf + 3], lp[4 * hf], lp[4 * hf + 2], lp[4 * hf + 1], lp[4 * hf + 3]);
         }
     };
-    // E + F: rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column of the finished tile -> f32 (u16: rounded), stored at once.  Buffer
+    // E + F: rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column of the finished tile -> f32 (16-bit types: rounded), stored at once.  Buffer
     // stores: rows past the image, pixels right of it and tiles that do not exist get an offset outside the resource
     const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows) * g.cols * static_cast<uint32_t>(ES * CH), kMxRsrcWord3);
     const uint32_t rowstep = ES * static_cast<uint32_t>(g.cols) * CH;
@@ -326,13 +369,14 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
     auto emit_store = [&](int tile, bool valid, int gq) __attribute__((always_inline)) {
         const int row0 = 32 * tile + 8 * gq + 4 * h;
         const uint32_t base = ES * ((static_cast<uint32_t>(row0) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c));
-        if constexpr (U16) {
+        if constexpr (W16) {
             uint32_t u[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int reg = 4 * gq + k;
                 const float v = __builtin_fmaf(tfin[reg] * kMxUnscale, unscale, (reg & 1) ? cneg : cpos);
-                u[k] = static_cast<uint32_t>(static_cast<int>(v + 0.5f)) & 0xffffu;          // add 0.5, truncate, keep the low 16 bits
+                if constexpr (HALF) u[k] = ff_half_round<T>(v);                               // one rounding to nearest even
+                else u[k] = static_cast<uint32_t>(static_cast<int>(v + 0.5f)) & 0xffffu;     // add 0.5, truncate, keep the low 16 bits
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -432,10 +476,11 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
 // The classes that are instantiated: all but NKB = 23 with 3 or 4 channels, whose strided loads leave no registers for the window
 // (768 bytes of scratch per lane); those take the plane fallback
 __host__ __device__ constexpr bool ff_class_ok(int nkb, int ch) { return !(nkb >= 23 && ch != 1); }
-// u16: every class fits (NKB 23 with 3 / 4 channels: 256 VGPRs, 234 / 223 AGPRs, no scratch)
+// u16: every class fits (NKB 23 with 3 / 4 channels: 256 VGPRs, 234 / 223 AGPRs, no scratch); the half types hold the same loads
+// and one window operand fewer: every class fits
 template <typename T> __host__ __device__ constexpr bool ff_class_ok_t(int nkb, int ch)
 {
-    return std::is_same_v<T, uint16_t> || ff_class_ok(nkb, ch);
+    return std::is_same_v<T, uint16_t> || ff_is_half_v<T> || ff_class_ok(nkb, ch);
 }
 // The classes the library's own choice takes.  The f32 accumulation over 2 x 3 products per window block reaches 1.02e-6 (NKB 19)
 // and 1.11e-6 (NKB 21, 23) of max|x| where the output is as large as max|x| over an area (steps, constants), and 1.19e-6 at NKB 17
@@ -445,16 +490,18 @@ __host__ __device__ constexpr bool ff_class_in_contract(int nkb) { return nkb <=
 
 template <typename T> struct FfEntryT {
     int nkb;
-    // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (float: qk.mbits always is; u16: never read)
+    // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (float and the half types: qk.mbits always is; u16: never read)
     hipError_t (*blur)(hipStream_t, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk, const T* strips);
 };
 using FfEntry = FfEntryT<float>;
 using FfEntryU16 = FfEntryT<uint16_t>;
+using FfEntryF16 = FfEntryT<ff_f16>;
+using FfEntryBf16 = FfEntryT<ff_bf16>;
 
 template <typename T, int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int num_cus, const FfQuirk& qk,
                                                                bool quirk, const T* strips)
 {
-    using C = FfCfg<NKB>;
+    using C = FfCfg<NKB, ff_is_half_v<T> ? 1 : 2>;
     const FxLaunch l = fx_plan_launch(g, CH, C::NT, num_cus);
     if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
@@ -499,6 +546,24 @@ template <typename T, int NKB> hipError_t ff_launch(hipStream_t st, const T* src
     }                                                                                                       \
     }
 
+// the float16 / bfloat16 instantiations: translation units of their own (ff_f16_conv_<NKB>.hip, ff_bf16_conv_<NKB>.hip)
+#define BLUR_FF_F16(NKB_)                                                                                   \
+    namespace blur_amd {                                                                                    \
+    const FfEntryF16* ff_f16_entry_##NKB_()                                                                 \
+    {                                                                                                       \
+        static const FfEntryF16 e = { NKB_, ff_launch<ff_f16, NKB_> };                                      \
+        return &e;                                                                                          \
+    }                                                                                                       \
+    }
+#define BLUR_FF_BF16(NKB_)                                                                                  \
+    namespace blur_amd {                                                                                    \
+    const FfEntryBf16* ff_bf16_entry_##NKB_()                                                               \
+    {                                                                                                       \
+        static const FfEntryBf16 e = { NKB_, ff_launch<ff_bf16, NKB_> };                                    \
+        return &e;                                                                                          \
+    }                                                                                                       \
+    }
+
 // ---- what runs before the fused kernel (engine.hip) ------------------------------------------------------------------
 // strips[f][strip][row][CH (128 + 2 pada)] samples: the window of an edge chunk with the mirrored pixels in place.  A thread moves
 // one sample.
@@ -520,7 +585,8 @@ __device__ __forceinline__ void ff_edge_strips_body(const T* __restrict__ src, T
 // 256 (CH = 1, 4) or 255 (CH = 3): element j BS + t of the batch belongs to thread t, so that all of a thread's elements are of
 // channel t mod CH.  Always: max|x| of the frame into mbits (integer atomicMax on the bits: order-free).  With `sums`: the parts of
 // Srow per batch (spart[f][batch][row][CH]) and the column sums per band (cpart), f32 products summed in double, every sum in a
-// fixed order.  u16 samples: no max (mbits is not touched); the sums hold integers below 2^53, exact in any order.
+// fixed order.  u16 samples: no max (mbits is not touched); the sums hold integers below 2^53, exact in any order.  float16 /
+// bfloat16 samples: widened to f32 (exact), then as float samples.
 constexpr int kFfSumRows = 16;
 __host__ __device__ constexpr int ff_batch_stride(int ch) { return ch == 3 ? 255 : 256; }
 inline int ff_groups_per_thread(int cols, int ch)
@@ -565,6 +631,8 @@ __device__ __forceinline__ void ff_altsums_body(const T* __restrict__ src, unsig
 #pragma unroll
             for (int j = 0; j < G; ++j) {
                 if constexpr (U16) v[j] = static_cast<float>(__builtin_amdgcn_raw_buffer_load_b16(rimg, own[j] ? 2u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
+                else if constexpr (ff_is_half_v<T>)
+                    v[j] = ff_half_widen<T>(__builtin_amdgcn_raw_buffer_load_b16(rimg, own[j] ? 2u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
                 else v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rimg, own[j] ? 4u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
             }
             if constexpr (!U16) {

@@ -228,6 +228,40 @@ int blur_gaussian_u16_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst,
 int blur_gaussian_u16_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, double sigma,
                            const blur_opts* opts);
 
+/* float16 (IEEE binary16: blur_gaussian_f16_*) and bfloat16 (blur_gaussian_bf16_*) frames of 1, 3 or 4 channels, interleaved,
+   rows*cols*channels samples per frame, nframes back to back, DEVICE pointers to the samples' BIT PATTERNS (this header is C and
+   has no 16-bit floating type: pass a torch.float16 / torch.bfloat16 tensor's data pointer, an _Float16 or __bf16 array; 2-byte
+   aligned, any element offset).  Every channel is blurred on its own exactly as pffft_() blurs one of its planes (sizing and
+   kernel from (rows, cols, sigma), reflect-101, the Nyquist-slot quirk per channel plane unless opts->nyquist_quirk = 0).  With v
+   the float plane (what blur_gaussian_f32_* computes for the same frame widened to float, which is exact for both types) the
+   output sample is v rounded ONCE to the sample type, to nearest even: binary16 as the float -> half conversion defines it
+   (subnormals kept, |v| past 65504 becomes +-Inf: with the quirk on, a frame near the type's largest value can overflow);
+   bfloat16 likewise (8 significant bits, float32's range).  No clamping and no + 0.5.  Parity: with ref the float64 reference plane,
+   m = max|x| of the frame and tol = 1e-6 m (the float entry's bound), the sample lies in [RN(ref - tol), RN(ref + tol)], RN the
+   rounding to the sample type; where the two ends are equal the sample is exactly the correctly rounded reference.  The frame is
+   scaled by a power of two taken from its own max|x| (found on the device, nothing waits for the host), as a float frame is.
+   opts->engine as for blur_gaussian_f32_*: AUTO takes the fused matrix-core kernel for pad <= 104 (frames of at most 4 GiB - 4 KiB)
+   and the f32 plane path per channel elsewhere; FUSED runs the fused kernel wherever one exists (pad <= 168, every channel count)
+   and fails with BLUR_ERR_UNSUPPORTED elsewhere; FFT always takes the plane path; other engines are BLUR_ERR_UNSUPPORTED.
+   blur_last_engine reports 6 (fused) or 0 (plane path).  The call is asynchronous on the context's stream.  Results are
+   bit-reproducible: a frame gives the same bits alone and inside a batch.  d_dst may equal d_src; other overlaps are detected
+   over the whole batch and read from a copy.  NaN or +-Inf in the input: unspecified values in that frame, no fault.
+   BLUR_ERR_INVALID: channels not in {1, 3, 4}, a NULL pointer, nframes < 0, rows, cols or sigma <= 0; BLUR_ERR_UNSUPPORTED:
+   pad > min(rows, cols) - 1.  These are checked before the device is touched (ctx may then be NULL); nframes == 0 is a no-op. */
+int blur_gaussian_f16_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                double sigma, const blur_opts* opts);
+int blur_gaussian_f16_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, double sigma,
+                          const blur_opts* opts);
+/* the same for one frame in HOST memory: copy in, blur, copy out, synchronise */
+int blur_gaussian_f16_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, double sigma,
+                           const blur_opts* opts);
+int blur_gaussian_bf16_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                 double sigma, const blur_opts* opts);
+int blur_gaussian_bf16_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, double sigma,
+                           const blur_opts* opts);
+int blur_gaussian_bf16_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, double sigma,
+                            const blur_opts* opts);
+
 /* HOST pointers: copy in, blur, copy out, synchronise (what a cv::Mat caller needs). */
 int blur_gaussian_u8c3_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst,
                             int rows, int cols, double sigma, const blur_opts* opts);
@@ -367,6 +401,15 @@ int blur_gaussian_u16_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint
                                       double sigma, const blur_opts* opts);
 int blur_gaussian_u16_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
                                        double sigma, const blur_opts* opts);
+/* blur_gaussian_f16_batch_dev / blur_gaussian_bf16_batch_dev over a batch, sharded by frame exactly like the calls above */
+int blur_gaussian_f16_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                      double sigma, const blur_opts* opts);
+int blur_gaussian_f16_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
+                                       double sigma, const blur_opts* opts);
+int blur_gaussian_bf16_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                       double sigma, const blur_opts* opts);
+int blur_gaussian_bf16_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
+                                        double sigma, const blur_opts* opts);
 /* fastboxblur over a batch, sharded by frame exactly like the two calls above, in place (blur_fastboxblur_u8_batch_dev on
    each shard); arguments and errors as blur_fastboxblur_u8_batch_dev, nframes == 0 is a no-op, shards without frames idle. */
 int blur_fastboxblur_u8_batch_multi_dev(blur_multi* m, uint8_t* d_inout, int nframes, int w, int h, int channels,

@@ -237,6 +237,21 @@ inline void gaussian_blur(uint16_t* data, int rows, int cols, int channels, doub
     check(ctx, blur_gaussian_u16_host(ctx, data, data, rows, cols, channels, sigma, opts), "gaussian_blur");
 }
 
+// float16 (IEEE binary16) and bfloat16 images of 1, 3 or 4 channels, in place, given as the samples' bit patterns (named, not
+// overloads: gaussian_blur(uint16_t*, ...) is the u16 call).  Every channel blurred on its own as pffft_ blurs one of its planes;
+// the float result rounded once to the sample type, to nearest even (blur_gaussian_f16_host / blur_gaussian_bf16_host)
+inline void gaussian_blur_f16(uint16_t* bits, int rows, int cols, int channels, double sigma, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f16_host(ctx, bits, bits, rows, cols, channels, sigma, opts), "gaussian_blur_f16");
+}
+
+inline void gaussian_blur_bf16(uint16_t* bits, int rows, int cols, int channels, double sigma, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_bf16_host(ctx, bits, bits, rows, cols, channels, sigma, opts), "gaussian_blur_bf16");
+}
+
 // pocketfft_1D(image, sigma) (Source.cpp:280-392) and pocketfft_2D(image, sigma) (Source.cpp:143-277): the two
 // pocketfft paths multiply all N/2+1 bins with the kernel's own spectrum (no Nyquist-slot quirk) and, inside the
 // cropped image, both equal the linear convolution of the reflect-101 extended image -- the engine's
