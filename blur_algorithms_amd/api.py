@@ -194,6 +194,38 @@ def _gauss_tensor(image, out, dtype, device=None):
     return t, dst, shape
 
 
+def _is_sigma_sequence(sigma):
+    """whether `sigma` is one value per channel (a list, tuple, numpy array or tensor of numbers) rather than a scalar.  A 0-d
+    numpy array or tensor is a scalar, as it was before sequences were accepted"""
+    if getattr(sigma, "ndim", 1) == 0:
+        return False
+    return hasattr(sigma, "__len__") and not isinstance(sigma, (str, bytes))
+
+
+def _sigma_arg(sigma, ch, two_d=False):
+    """the `sigma` argument of a per-channel Gaussian entry: a float, or for a sequence a double[ch] for the _sigmas_ entries (0 = the
+    channel is left as it is).  The sequence has one entry per channel; two_d: a [rows, cols] image takes a sequence of one"""
+    if not _is_sigma_sequence(sigma):
+        return float(sigma)
+    vals = [float(v) for v in sigma]
+    if len(vals) != ch:
+        raise ValueError("sigma: expected a number or a sequence of %d (one per channel%s), got %d"
+                         % (ch, " of the [rows, cols] image" if two_d else "", len(vals)))
+    return (C.c_double * ch)(*vals)
+
+
+def gaussian_sigmas_plan(rows, cols, sigmas):
+    """how a per-channel-sigma Gaussian call groups its channels (host only, no GPU): a list with one (group, pad, nkb) per channel.
+    group: channels of equal sigma share an index, -1 for sigma = 0 (the channel is copied); pad: pffft_sizing's; nkb: the fused
+    kernel's window class, 0 where the pad has none (pad > 168: the plane path)"""
+    vals = [float(v) for v in sigmas]
+    out = (C.c_int * (3 * len(vals)))()
+    rc = _L().blur_gaussian_sigmas_plan(int(rows), int(cols), len(vals), (C.c_double * max(1, len(vals)))(*vals), out)
+    if rc:
+        raise BlurError(rc, "gaussian_sigmas_plan: bad arguments")
+    return [(out[3 * c], out[3 * c + 1], out[3 * c + 2]) for c in range(len(vals))]
+
+
 def fft_plan_radices(n):
     r = (C.c_int * 16)()
     k = _L().blur_fft_plan_radices(int(n), r)
@@ -528,11 +560,14 @@ class BlurContext:
         """Gaussian blur of a 1-, 3- or 4-channel uint8 image (grayscale, BGR, BGRA / RGBA): [rows, cols], [rows, cols, C] or a batch
         [n, rows, cols, C], C in {1, 3, 4}.  Every channel, alpha included, is blurred on its own exactly as pffft_ blurs one of
         its three (blur_gaussian_u8_batch_dev).  engine: None (the library's choice), "fused" or "fft".
+        sigma: a number, or a sequence of C numbers, one per channel (blur_gaussian_u8_sigmas_batch_dev): channel c is blurred as the
+        scalar call with sigma[c] blurs it, and 0 leaves the channel as it is (BGRA with (s, s, s, 0): the alpha is untouched).  The
+        same holds for gaussian_f32, gaussian_u16, gaussian_f16 and gaussian_bf16.
 
         torch CUDA tensor: asynchronous on torch's current stream, returns `out` (default: in place, like pffft_).  numpy array:
         host round trip, returns a new array.
         """
-        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.uint8, self._lib.blur_gaussian_u8_host, self._lib.blur_gaussian_u8_batch_dev)
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.uint8, "u8")
 
     def gaussian_f32(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
         """Gaussian blur of a float32 image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows, cols, C].  Every
@@ -542,8 +577,7 @@ class BlurContext:
         torch CUDA tensor: asynchronous on torch's current stream, returns `out` (default: in place).  numpy array: host round trip,
         returns a new array.
         """
-        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.float32, self._lib.blur_gaussian_f32_host,
-                              self._lib.blur_gaussian_f32_batch_dev)
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.float32, "f32")
 
     def gaussian_u16(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
         """Gaussian blur of a uint16 image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows, cols, C].  Every
@@ -553,8 +587,7 @@ class BlurContext:
         torch CUDA tensor (torch.uint16): asynchronous on torch's current stream, returns `out` (default: in place).  numpy array:
         host round trip, returns a new array.
         """
-        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.uint16, self._lib.blur_gaussian_u16_host,
-                              self._lib.blur_gaussian_u16_batch_dev)
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.uint16, "u16")
 
     def gaussian_f16(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
         """Gaussian blur of a float16 (IEEE binary16) image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows,
@@ -565,8 +598,7 @@ class BlurContext:
         torch CUDA tensor (torch.float16): asynchronous on torch's current stream, returns `out` (default: in place).  numpy float16
         array: host round trip, returns a new array.  A uint16 array is refused: it is a u16 image (gaussian_u16).
         """
-        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.float16, self._lib.blur_gaussian_f16_host,
-                              self._lib.blur_gaussian_f16_batch_dev)
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.float16, "f16")
 
     def gaussian_bf16(self, image, sigma, out=None, nyquist_quirk=True, engine=None):
         """Gaussian blur of a bfloat16 image of 1, 3 or 4 channels: [rows, cols], [rows, cols, C] or a batch [n, rows, cols, C].  Every
@@ -576,20 +608,26 @@ class BlurContext:
         torch CUDA tensor (torch.bfloat16): asynchronous on torch's current stream, returns `out` (default: in place).  CPU
         torch.bfloat16 tensor: host round trip, returns a new CPU tensor (numpy has no bfloat16; a numpy array is refused).
         """
-        return self._gaussian(image, sigma, out, nyquist_quirk, engine, BF16, self._lib.blur_gaussian_bf16_host,
-                              self._lib.blur_gaussian_bf16_batch_dev)
+        return self._gaussian(image, sigma, out, nyquist_quirk, engine, BF16, "bf16")
 
-    def _gaussian(self, image, sigma, out, nyquist_quirk, engine, dtype, host_entry, batch_dev_entry):
+    def _gaussian(self, image, sigma, out, nyquist_quirk, engine, dtype, tname):
+        """tname: the entry points' type name (blur_gaussian_<tname>_host, _batch_dev; a sequence `sigma`: _sigmas_host, _sigmas_batch_dev)"""
         o = self._opts(nyquist_quirk, engine=engine)
+        per_channel = _is_sigma_sequence(sigma)
+        mid = "_sigmas" if per_channel else ""
         if _is_host_frames(image, dtype):
             a, res, (n, rows, cols, ch) = _gauss_array(image, out, dtype)
+            sg = _sigma_arg(sigma, ch, a.ndim == 2)
+            host_entry = getattr(self._lib, "blur_gaussian_%s%s_host" % (tname, mid))
             fb = rows * cols * ch * a.itemsize
             for f in range(n):
-                self._check(host_entry(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch, float(sigma), C.byref(o)))
+                self._check(host_entry(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch, sg, C.byref(o)))
             return _gauss_result(res, out, dtype)
         t, dst, (n, rows, cols, ch) = _gauss_tensor(image, out, dtype)
+        sg = _sigma_arg(sigma, ch, t.dim() == 2)
         self.use_torch_stream()
-        self._check(batch_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
+        batch_dev_entry = getattr(self._lib, "blur_gaussian_%s%s_batch_dev" % (tname, mid))
+        self._check(batch_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, sg, C.byref(o)))
         return dst
 
     def fastboxblur(self, image, ksize, passes):
@@ -680,47 +718,45 @@ class BlurMulti:
     def gaussian(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
         """BlurContext.gaussian over a batch sharded by frame: frames uint8 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
         tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
-        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.uint8, self._lib.blur_gaussian_u8_batch_multi_host,
-                              self._lib.blur_gaussian_u8_batch_multi_dev)
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.uint8, "u8")
 
     def gaussian_f32(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
         """BlurContext.gaussian_f32 over a batch sharded by frame: frames float32 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
         tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
-        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.float32, self._lib.blur_gaussian_f32_batch_multi_host,
-                              self._lib.blur_gaussian_f32_batch_multi_dev)
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.float32, "f32")
 
     def gaussian_u16(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
         """BlurContext.gaussian_u16 over a batch sharded by frame: frames uint16 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
         tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
-        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.uint16, self._lib.blur_gaussian_u16_batch_multi_host,
-                              self._lib.blur_gaussian_u16_batch_multi_dev)
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.uint16, "u16")
 
     def gaussian_f16(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
         """BlurContext.gaussian_f16 over a batch sharded by frame: frames float16 [n, rows, cols, C], C in {1, 3, 4}; a torch CUDA
         tensor on devices[0] (default: in place) or a numpy array in host memory (a new array).  Synchronous."""
-        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.float16, self._lib.blur_gaussian_f16_batch_multi_host,
-                              self._lib.blur_gaussian_f16_batch_multi_dev)
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, np.float16, "f16")
 
     def gaussian_bf16(self, frames, sigma, out=None, nyquist_quirk=True, engine=None):
         """BlurContext.gaussian_bf16 over a batch sharded by frame: frames torch.bfloat16 [n, rows, cols, C], C in {1, 3, 4}; a CUDA
         tensor on devices[0] (default: in place) or a CPU tensor (a new CPU tensor).  Synchronous."""
-        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, BF16, self._lib.blur_gaussian_bf16_batch_multi_host,
-                              self._lib.blur_gaussian_bf16_batch_multi_dev)
+        return self._gaussian(frames, sigma, out, nyquist_quirk, engine, BF16, "bf16")
 
-    def _gaussian(self, frames, sigma, out, nyquist_quirk, engine, dtype, multi_host_entry, multi_dev_entry):
+    def _gaussian(self, frames, sigma, out, nyquist_quirk, engine, dtype, tname):
         o = BlurOpts()
         self._lib.blur_opts_default(C.byref(o))
         o.nyquist_quirk = 1 if nyquist_quirk else 0
         if engine is not None:
             o.engine = ENGINES[engine]
+        mid = "_sigmas" if _is_sigma_sequence(sigma) else ""
         if _is_host_frames(frames, dtype):
             a, res, (n, rows, cols, ch) = _gauss_array(frames, out, dtype, batch=True)
-            self._check(multi_host_entry(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, float(sigma), C.byref(o)))
+            multi_host_entry = getattr(self._lib, "blur_gaussian_%s%s_batch_multi_host" % (tname, mid))
+            self._check(multi_host_entry(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, _sigma_arg(sigma, ch), C.byref(o)))
             return _gauss_result(res, out, dtype)
         import torch
         t, dst, (n, rows, cols, ch) = _gauss_tensor(frames, out, dtype, device=self.devices[0])
         torch.cuda.synchronize(t.device)
-        self._check(multi_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, float(sigma), C.byref(o)))
+        multi_dev_entry = getattr(self._lib, "blur_gaussian_%s%s_batch_multi_dev" % (tname, mid))
+        self._check(multi_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, _sigma_arg(sigma, ch), C.byref(o)))
         return dst
 
     def fastboxblur(self, frames, ksize, passes):

@@ -16,6 +16,7 @@
 // HBM traffic per pixel: 3 B in + 12 B intermediate out, 12 B intermediate in + 3 B out.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1738,7 +1739,9 @@ static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
 
 // the fused kernel for CH = 1, 4 (fw_kernels.hpp): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
 // Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).
-static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
+// chsel: the channels to blur (blur_ch_sigmas_batch_impl: one sigma per channel); the pre-pass reads every channel (a pixel is one
+// dword) and completes the quirk's row sums of these channels only
+static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel)
 {
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
     const FcEntry* fe = find_fc_entry(nkb);
@@ -1781,11 +1784,11 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
         auto kern = ch == 1 ? (G == 1 ? fc_prepass<1, 1> : (G == 2 ? fc_prepass<1, 2> : fc_prepass<1, 4>))
                             : (G == 1 ? fc_prepass<4, 1> : (G == 2 ? fc_prepass<4, 2> : fc_prepass<4, 4>));
         hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, p.sz.pad, pada, nbands,
-                           nbatches, cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows);
+                           nbatches, cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel));
         HIP_TRY(ctx, hipGetLastError());
     }
     TimedLaunch t(ctx, 0, nframes);
-    HIP_TRY(ctx, fe->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips));
+    HIP_TRY(ctx, fe->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel));
     return BLUR_OK;
 }
 
@@ -1793,9 +1796,9 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
 // then the kernel.  Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).  Every
 // partition of a sum (bands, batches) depends on the frame's shape only: a frame gives the same bits alone and in a batch.
 // T = float, uint16_t, ff_f16 or ff_bf16.  u16: no max|x| (the scale is a constant of the call), and without the quirk no sums at
-// all; the half types: as float.
+// all; the half types: as float.  chsel: the channels to blur (the pre-pass covers every channel either way: max|x| is the frame's).
 template <typename T>
-static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p)
+static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel)
 {
     constexpr bool u16 = std::is_same_v<T, uint16_t>;
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
@@ -1857,7 +1860,7 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
         }
     }
     TimedLaunch t(ctx, 0, nframes);
-    HIP_TRY(ctx, fe->blur(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, strips));
+    HIP_TRY(ctx, fe->blur(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, strips, chsel));
     return BLUR_OK;
 }
 
@@ -1892,12 +1895,13 @@ __device__ inline int chan_scale_exp(unsigned mbits)
 }
 
 template <typename T>
-__global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes, size_t px, int ch, const unsigned* __restrict__ mbits)
+__global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes, size_t px, int ch, const unsigned* __restrict__ mbits, unsigned mask)
 {
     float scale = 1.f;
     if constexpr (std::is_same_v<T, float> || ff_is_half_v<T>) scale = ldexpf(1.f, chan_scale_exp(*mbits));
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
         for (int c = 0; c < ch; ++c) {
+            if (!(mask >> c & 1u)) continue;
             if constexpr (std::is_same_v<T, float>) planes[c * px + i] = src[i * ch + c] * scale;
             else if constexpr (ff_is_half_v<T>) planes[c * px + i] = chan_widen(src[i * ch + c]) * scale;
             else planes[c * px + i] = static_cast<float>(src[i * ch + c]);
@@ -1905,12 +1909,13 @@ __global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes
 }
 
 template <typename T>
-__global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst, size_t px, int ch, const unsigned* __restrict__ mbits)
+__global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst, size_t px, int ch, const unsigned* __restrict__ mbits, unsigned mask)
 {
     float unscale = 1.f;
     if constexpr (std::is_same_v<T, float> || ff_is_half_v<T>) unscale = ldexpf(1.f, -chan_scale_exp(*mbits));
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
         for (int c = 0; c < ch; ++c) {
+            if (!(mask >> c & 1u)) continue;
             if constexpr (std::is_same_v<T, uint8_t>)  // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
                 dst[i * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffu);
             else if constexpr (std::is_same_v<T, uint16_t>)  // the same rule 16 bits wide: truncate, keep the low 16 bits
@@ -1922,8 +1927,9 @@ __global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst,
         }
 }
 
+// mask: the channels to blur (one sigma per channel: the others are neither split nor packed; max|x| is the whole frame's either way)
 template <typename T>
-static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts)
+static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts, unsigned mask = 0xfu)
 {
     Prepared p;
     if (int rc = prepare(ctx, rows, cols, sigma, opts, p, false)) return rc;
@@ -1940,14 +1946,15 @@ static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int 
             hipLaunchKernelGGL(chan_maxabs<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, mbits, px * ch);
             HIP_TRY(ctx, hipGetLastError());
         }
-        hipLaunchKernelGGL(chan_split<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch, mbits);
+        hipLaunchKernelGGL(chan_split<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch, mbits, mask);
         HIP_TRY(ctx, hipGetLastError());
         for (int c = 0; c < ch; ++c) {
+            if (!(mask >> c & 1u)) continue;
             float* plane = ctx->ch_planes + c * px;
             if (int rc = launch_rowpass<float, 1>(ctx, plane, ctx->work, rows, cols, p.sz.pad, *p.row, p.m_row)) return rc;
             if (int rc = launch_colpass<float, 1>(ctx, ctx->work, plane, rows, cols, p.sz.pad, *p.col, p.m_col, p.col_group)) return rc;
         }
-        hipLaunchKernelGGL(chan_pack<T>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch, mbits);
+        hipLaunchKernelGGL(chan_pack<T>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch, mbits, mask);
         HIP_TRY(ctx, hipGetLastError());
     }
     return BLUR_OK;
@@ -1965,30 +1972,17 @@ static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nf
     return ctx ? BLUR_OK : BLUR_ERR_INVALID;
 }
 
-// One driver for the five element types (float16 and bfloat16: in everything below as float32, two bytes per sample).  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused
-// kernel for NKB 23 with 3 or 4 channels (ff_class_ok_t); the own choice of float32 and u16 stops at NKB 15 (ff_class_in_contract: at 16 bits
-// 1e-6 of full scale is 0.066 of a grey level); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 / run_ff<T>)
-// and the engine error's text
+// The engine of a per-channel blur with one sigma (blur_ch_batch_impl; blur_ch_sigmas_batch_impl: of a group of channels): p.fx set =
+// the fused kernel, else the plane fallback, and `note` says why.  choice: AUTO, FUSED or FFT.
 template <typename T>
-static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+static int choose_ch_engine(blur_ctx* ctx, int rows, int cols, int channels, double sigma, const blur_opts* opts, int choice, Prepared& p, std::string& note)
 {
-    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;      // ffk: the ff_kernels.hpp types
-    if (int rc = check_ch_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma)) return rc;
-    if constexpr (u8) {
-        if (channels == 3) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
-    }
-    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
-    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, half ? (std::string(ch_type_name<T>()) + " images: engine must be AUTO, FUSED or FFT").c_str()
-                                                    : (u16 ? "u16 images: engine must be AUTO, FUSED or FFT"
-                                                           : (ffk ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT")));
+    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;
     // The fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED: a kernel for the pad, the frame and quirk limits; a
     // float32 class instantiated for the channel count; the frame's bytes within 32-bit offsets), the plane fallback elsewhere.  AUTO
     // too: where the u8c3 policy passes the fused engine over for a compile-time FFT family (frames under 1 MP, pad > 152 on 6 MP), the
     // alternative here is the run-time-planned plane path, three to four times slower than the fused kernel (4K sigma 50, 8 frames:
     // 0.146 ms per 1-channel u8 frame, 0.568 per 4-channel one, on the plane path)
-    Prepared p;
-    std::string note;
     if (choice != BLUR_ENGINE_FFT) {
         blur_opts fo;
         blur_opts_default(&fo);
@@ -2014,6 +2008,29 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
             note = why;
         }
     }
+    return BLUR_OK;
+}
+
+// One driver for the five element types (float16 and bfloat16: in everything below as float32, two bytes per sample).  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused
+// kernel for NKB 23 with 3 or 4 channels (ff_class_ok_t); the own choice of float32 and u16 stops at NKB 15 (ff_class_in_contract: at 16 bits
+// 1e-6 of full scale is 0.066 of a grey level); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 / run_ff<T>)
+// and the engine error's text
+template <typename T>
+static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;      // ffk: the ff_kernels.hpp types
+    if (int rc = check_ch_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma)) return rc;
+    if constexpr (u8) {
+        if (channels == 3) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
+    }
+    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
+    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, half ? (std::string(ch_type_name<T>()) + " images: engine must be AUTO, FUSED or FFT").c_str()
+                                                    : (u16 ? "u16 images: engine must be AUTO, FUSED or FFT"
+                                                           : (ffk ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT")));
+    Prepared p;
+    std::string note;
+    if (int rc = choose_ch_engine<T>(ctx, rows, cols, channels, sigma, opts, choice, p, note)) return rc;
     if (nframes == 0) return BLUR_OK;
     const size_t fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(T);
     // overlap of the source and destination ranges (over the whole batch): the fused kernel reads its neighbours' pixels while it
@@ -2040,8 +2057,8 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
     }
     if (p.fx) {
         ctx->last_family = 6;
-        if constexpr (ffk) return run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
-        else return run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p);
+        if constexpr (ffk) return run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels));
+        else return run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels));
     }
     blur_opts o;
     blur_opts_default(&o);
@@ -2066,6 +2083,184 @@ static int blur_ch_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols,
     int rc = BLUR_OK;
     hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) rc = blur_ch_batch_impl(ctx, reinterpret_cast<const T*>(d), reinterpret_cast<T*>(d + half), 1, rows, cols, channels, sigma, opts);
+    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
+    return rc;
+}
+
+// ======================================================================================
+// One sigma per channel (blur_gaussian_{u8,f32,u16,f16,bf16}_sigmas_*): channel c is what the scalar entry returns for sigmas[c];
+// sigma = 0 leaves the channel as it is
+// ======================================================================================
+static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump, FwChSel chsel);
+
+// The channels of a call by sigma: group g holds the channels in mask[g] with sigma[g] > 0, in the order of their first channel;
+// zero_mask: the channels with sigma = 0
+struct SigmaGroups {
+    int ngroups = 0;
+    double sigma[4] = {};
+    unsigned mask[4] = {};
+    int group_of[4] = { -1, -1, -1, -1 };
+    unsigned zero_mask = 0;
+};
+
+// The arguments of every blur_gaussian_*_sigmas_* entry, without a context or a device: the status and, where it is not BLUR_OK,
+// its text in *why.  Every entry of sigmas is checked here, before anything is launched: a refused call has written nothing.
+static int ch_sigmas_status(const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, SigmaGroups& sg, const char** why)
+{
+    auto no = [&](int rc, const char* text) { *why = text; return rc; };
+    if (channels != 1 && channels != 3 && channels != 4) return no(BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
+    if (!src || !dst || nframes < 0) return no(BLUR_ERR_INVALID, "null frame pointer or negative frame count");
+    if (rows <= 0 || cols <= 0) return no(BLUR_ERR_INVALID, "rows and cols must be positive");
+    if (!sigmas) return no(BLUR_ERR_INVALID, "sigmas must point to one sigma per channel");
+    for (int c = 0; c < channels; ++c)
+        if (!(sigmas[c] >= 0) || !std::isfinite(sigmas[c])) return no(BLUR_ERR_INVALID, "every sigma must be finite and positive, or 0 for a channel that is left as it is");
+    sg = SigmaGroups{};
+    for (int c = 0; c < channels; ++c) {
+        if (sigmas[c] == 0) { sg.zero_mask |= 1u << c; continue; }
+        int g = 0;
+        while (g < sg.ngroups && sg.sigma[g] != sigmas[c]) ++g;
+        if (g == sg.ngroups) sg.sigma[sg.ngroups++] = sigmas[c];
+        sg.mask[g] |= 1u << c;
+        sg.group_of[c] = g;
+    }
+    for (int g = 0; g < sg.ngroups; ++g) {
+        const Sizing sz = pffft_sizing(rows, cols, sg.sigma[g]);
+        if (sz.pad > rows - 1 || sz.pad > cols - 1)
+            return no(BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1 for one of the sigmas: reflect-101 would read outside the image (README.md:33-38)");
+    }
+    return BLUR_OK;
+}
+
+// the same for an entry with a context: the arguments' status first (ctx = NULL: the status is the same), then the missing context
+static int check_ch_sigmas_args(blur_ctx* ctx, const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, SigmaGroups& sg)
+{
+    const char* why = nullptr;
+    if (int rc = ch_sigmas_status(src, dst, nframes, rows, cols, channels, sigmas, sg, &why)) return fail(ctx, rc, why);
+    return ctx ? BLUR_OK : BLUR_ERR_INVALID;
+}
+
+// The sigma = 0 channels of an out-of-place call: the samples (ES bytes each) of the channels in `mask` of a CH-interleaved batch go
+// from src to dst.  The call runs before the blurred channels are written, on the same stream, and every channel outside the mask
+// is one of them, so the other bytes of dst may hold anything afterwards.  vec (both pointers 16-byte aligned): a lane moves 16
+// bytes of src as they are and dst is not read; the samples behind the last whole 16 bytes, and every sample where vec = 0, go
+// one by one, the masked channels only.
+template <int ES, int CH>
+__global__ __launch_bounds__(256) void chan_copy(const uint8_t* __restrict__ src, uint8_t* dst, size_t nbytes, unsigned mask, int vec)
+{
+    using E = std::conditional_t<ES == 1, uint8_t, std::conditional_t<ES == 2, uint16_t, uint32_t>>;
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x, t0 = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+    const size_t nv = vec ? nbytes / 16 : 0, ne = nbytes / ES;
+    for (size_t i = t0; i < nv; i += stride) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+    for (size_t e = nv * (16 / ES) + t0; e < ne; e += stride)
+        if (mask >> static_cast<unsigned>(e % CH) & 1u) reinterpret_cast<E*>(dst)[e] = reinterpret_cast<const E*>(src)[e];
+}
+
+template <typename T>
+static int launch_chan_copy(blur_ctx* ctx, const T* src, T* dst, size_t nelem, int ch, unsigned mask)
+{
+    constexpr int ES = sizeof(T);
+    const size_t nbytes = nelem * ES;
+    if (nbytes == 0 || !mask) return BLUR_OK;
+    const int vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 ? 1 : 0;
+    const size_t items = vec ? nbytes / 16 + 256 : nelem;
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((items + 255) / 256, 16384));
+    auto kern = ch == 3 ? chan_copy<ES, 3> : chan_copy<ES, 4>;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nbytes, mask, vec);
+    HIP_TRY(ctx, hipGetLastError());
+    return BLUR_OK;
+}
+
+// One driver for the five element types, next to blur_ch_batch_impl.  The channels are grouped by sigma; one group without zeros is
+// the scalar call itself.  Otherwise every group gets the engine blur_ch_batch_impl's rules give its sigma (choose_ch_engine; u8 with
+// three channels too: its groups run on fw_blur_u8<NKB, Q, 3> where the scalar u8c3 call has other kernels), all of them before the
+// first launch.  Overlapping frames, in place included, are read from one copy by every group.  Then, on the one stream: the copy of
+// the sigma = 0 channels (out of place only), and per group the whole pre-pass (the quirk's sums are weighted by the pad's parity and
+// the strips are as wide as the pad: both belong to the group) and the fused launch over the group's channels, or the plane path
+// over them.  The strips and sums workspaces are reused from group to group.
+template <typename T>
+static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    constexpr bool u8 = std::is_same_v<T, uint8_t>;
+    SigmaGroups sg;
+    if (int rc = check_ch_sigmas_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, sg)) return rc;
+    if (sg.ngroups == 1 && !sg.zero_mask) return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[0], opts);
+    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
+    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, (std::string(ch_type_name<T>()) + " images, one sigma per channel: engine must be AUTO, FUSED or FFT").c_str());
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Prepared p[4];
+    std::string why[4];
+    for (int g = 0; g < sg.ngroups; ++g)
+        if (int rc = choose_ch_engine<T>(ctx, rows, cols, channels, sg.sigma[g], opts, choice, p[g], why[g])) return rc;
+    ctx->engine_note.clear();
+    if (nframes == 0) return BLUR_OK;
+    const bool in_place = d_src == d_dst;
+    if (in_place && sg.ngroups == 0) return BLUR_OK;            // every channel is left as it is
+    const size_t fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(T);
+    const char* lo = reinterpret_cast<const char*>(d_src < d_dst ? d_src : d_dst);
+    const char* hi = reinterpret_cast<const char*>(d_src < d_dst ? d_dst : d_src);
+    if (static_cast<size_t>(hi - lo) < fb * nframes) {
+        if (in_place) {             // in parts of at most 1 GiB (a part's result never touches a later part's source)
+            const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
+            if (static_cast<size_t>(nframes) > cap) {
+                for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
+                    const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
+                    T* part = d_dst + static_cast<size_t>(f0) * fe;
+                    if (int rc = blur_ch_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas, opts)) return rc;
+                }
+                return BLUR_OK;
+            }
+        }
+        if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
+        d_src = reinterpret_cast<const T*>(ctx->ch_copy);
+    }
+    if (!in_place) {
+        if (sg.ngroups == 0) HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
+        else if (int rc = launch_chan_copy<T>(ctx, d_src, d_dst, fe * nframes, channels, sg.zero_mask)) return rc;       // (every other channel is written below)
+    }
+    blur_opts fft_opts;
+    blur_opts_default(&fft_opts);
+    if (opts) fft_opts = *opts;
+    fft_opts.engine = BLUR_ENGINE_FFT;
+    std::string note;
+    for (int g = 0; g < sg.ngroups; ++g) {
+        if (p[g].fx) {
+            const FwChSel chsel = fw_chsel_mask(sg.mask[g], channels);
+            int rc;
+            if constexpr (!u8) rc = run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], chsel);
+            else rc = channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, nframes, rows, cols, p[g], nullptr, chsel)
+                                    : run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], chsel);
+            if (rc) return rc;
+        } else {
+            if (int rc = run_planes(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[g], &fft_opts, sg.mask[g])) return rc;
+            char head[96];
+            std::snprintf(head, sizeof head, "%ssigma %g (channel mask 0x%x) on the plane path: ", note.empty() ? "" : "; ", sg.sigma[g], sg.mask[g]);
+            note += head + why[g];
+        }
+    }
+    // family 6: every blurred group ran on the fused kernel; 0: a group took the plane path, and the note names it
+    ctx->last_family = note.empty() ? 6 : 0;
+    ctx->engine_note = note;
+    return BLUR_OK;
+}
+
+// blur_gaussian_*_sigmas_host: one frame through the context's host staging buffer (as blur_ch_host)
+template <typename T>
+static int blur_ch_sigmas_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    SigmaGroups sg;
+    if (int rc = check_ch_sigmas_args(ctx, src, dst, 1, rows, cols, channels, sigmas, sg)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = static_cast<size_t>(rows) * cols * channels * sizeof(T), half = (bytes + 255) & ~static_cast<size_t>(255);
+    void* dv = nullptr;
+    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;
+    char* d = static_cast<char*>(dv);
+    int rc = BLUR_OK;
+    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) rc = blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const T*>(d), reinterpret_cast<T*>(d + half), 1, rows, cols, channels, sigmas, opts);
     if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
@@ -2342,7 +2537,9 @@ static int run_mx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
 }
 
 // both passes in one kernel on the matrix cores (fx_kernels.hpp): no intermediate in memory
-static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump = nullptr)
+// chsel != 0 (blur_ch_sigmas_batch_impl: one sigma per channel): only these channels, on the one-channel-per-workgroup kernel of
+// the window class (Fw3Entry: whole-window strips)
+static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump = nullptr, FwChSel chsel = 0)
 {
     const size_t px = static_cast<size_t>(rows) * cols;
     // in place (the reference's own calling convention, Source.cpp:429,567): a strip reads its neighbours' columns and the rows
@@ -2356,7 +2553,7 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
         if (d_src == d_dst && static_cast<size_t>(nframes) > cap) {
             for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
                 const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
-                if (int rc = run_fx_u8c3(ctx, d_src + static_cast<size_t>(f0) * px * 3, d_dst + static_cast<size_t>(f0) * px * 3, nf, rows, cols, p, vdump)) return rc;
+                if (int rc = run_fx_u8c3(ctx, d_src + static_cast<size_t>(f0) * px * 3, d_dst + static_cast<size_t>(f0) * px * 3, nf, rows, cols, p, vdump, chsel)) return rc;
             }
             return BLUR_OK;
         }
@@ -2381,7 +2578,7 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
 #ifdef FX_FULL_STRIPS
         0;
 #else
-        p.fx->nkb <= 11 ? 1 : 0;
+        p.fx->nkb <= 11 && !chsel ? 1 : 0;
 #endif
     int strip_groups = (kFxChunk + 2 * pada) / 4;
     if (narrow) {
@@ -2442,6 +2639,13 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
     if (!p.mx_quirk && !vdump && std::getenv("BLUR_FX_STAMPS")) {
         HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&stamps), 64));
         HIP_TRY(ctx, hipMemset(stamps, 0, 64));
+    }
+    if (chsel) {
+        const Fw3Entry* fe3 = find_fw3_entry(nkb);
+        if (!fe3 || vdump || stamps) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for a subset of three channels: no kernel instantiated for this pad");
+        TimedLaunch t(ctx, 0, nframes);
+        HIP_TRY(ctx, fe3->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel));
+        return BLUR_OK;
     }
     { TimedLaunch t(ctx, 0, nframes);
       HIP_TRY(ctx, p.fx->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, vdump, stamps)); }
@@ -3544,6 +3748,192 @@ int blur_gaussian_bf16_batch_multi_host(blur_multi* m, const uint16_t* src, uint
                                        const blur_opts* opts)
 {
     return blur_ch_multi(m, reinterpret_cast<const ff_bf16*>(src), reinterpret_cast<ff_bf16*>(dst), nframes, rows, cols, channels, sigma, opts, 0);
+}
+
+// blur_gaussian_*_sigmas_batch_multi_*: as blur_ch_multi with one sigma per channel (each shard gets its own copy of the sigmas)
+extern "C++" {
+template <typename T>
+static int blur_ch_sigmas_multi(blur_multi* m, const T* src, T* dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts, int location)
+{
+    SigmaGroups sg;
+    const char* why = nullptr;
+    if (int rc = ch_sigmas_status(src, dst, nframes, rows, cols, channels, sigmas, sg, &why)) { if (m) m->err = why; return rc; }
+    if (!m) return BLUR_ERR_INVALID;
+    if (nframes == 0) return BLUR_OK;
+    if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
+    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels * sizeof(T) : 0;
+    const std::array<double, 4> sv = { sigmas[0], channels > 1 ? sigmas[1] : 0.0, channels > 2 ? sigmas[2] : 0.0, channels > 3 ? sigmas[3] : 0.0 };
+    return blur_multi_run(m, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nframes, fb, location,
+                          [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) {
+                              return blur_ch_sigmas_batch_impl(c, reinterpret_cast<const T*>(in), reinterpret_cast<T*>(out), n, rows, cols, channels, sv.data(), opts);
+                          });
+}
+}  // extern "C++"
+
+// host-only: how a call with these sigmas groups its channels
+int blur_gaussian_sigmas_plan(int rows, int cols, int channels, const double* sigmas, int* out)
+{
+    SigmaGroups sg;
+    int dummy = 0;
+    const char* why = nullptr;
+    if (!out) return BLUR_ERR_INVALID;
+    if (int rc = ch_sigmas_status(&dummy, &dummy, 0, rows, cols, channels, sigmas, sg, &why)) return rc;
+    for (int c = 0; c < channels; ++c) {
+        const int g = sg.group_of[c];
+        out[3 * c] = g;
+        out[3 * c + 1] = out[3 * c + 2] = 0;
+        if (g < 0) continue;
+        const int pad = pffft_sizing(rows, cols, sg.sigma[g]).pad;
+        const FxEntry* fe = find_fx_entry(pad);
+        out[3 * c + 1] = pad;
+        out[3 * c + 2] = fe ? fe->nkb : 0;
+    }
+    return BLUR_OK;
+}
+
+// u8 images, one sigma per channel
+int blur_gaussian_u8_sigmas_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                      const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_u8_sigmas_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_u8_sigmas_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_host(ctx, src, dst, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_u8_sigmas_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                            const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, 1);
+}
+
+int blur_gaussian_u8_sigmas_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                             const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, src, dst, nframes, rows, cols, channels, sigmas, opts, 0);
+}
+
+// float32 images, one sigma per channel
+int blur_gaussian_f32_sigmas_batch_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                       const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_f32_sigmas_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_f32_sigmas_host(blur_ctx* ctx, const float* src, float* dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_host(ctx, src, dst, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_f32_sigmas_batch_multi_dev(blur_multi* m, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                             const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, 1);
+}
+
+int blur_gaussian_f32_sigmas_batch_multi_host(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                              const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, src, dst, nframes, rows, cols, channels, sigmas, opts, 0);
+}
+
+// u16 images, one sigma per channel
+int blur_gaussian_u16_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                       const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_u16_sigmas_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, 1, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_u16_sigmas_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_host(ctx, src, dst, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_u16_sigmas_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                             const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, 1);
+}
+
+int blur_gaussian_u16_sigmas_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                              const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, src, dst, nframes, rows, cols, channels, sigmas, opts, 0);
+}
+
+// float16 (bit patterns) images, one sigma per channel
+int blur_gaussian_f16_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                       const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_f16_sigmas_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), 1, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_f16_sigmas_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_host(ctx, reinterpret_cast<const ff_f16*>(src), reinterpret_cast<ff_f16*>(dst), rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_f16_sigmas_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                             const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), nframes, rows, cols, channels, sigmas, opts, 1);
+}
+
+int blur_gaussian_f16_sigmas_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                              const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, reinterpret_cast<const ff_f16*>(src), reinterpret_cast<ff_f16*>(dst), nframes, rows, cols, channels, sigmas, opts, 0);
+}
+
+// bfloat16 (bit patterns) images, one sigma per channel
+int blur_gaussian_bf16_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                        const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_bf16_sigmas_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), 1, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_bf16_sigmas_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    return blur_ch_sigmas_host(ctx, reinterpret_cast<const ff_bf16*>(src), reinterpret_cast<ff_bf16*>(dst), rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_bf16_sigmas_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                              const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigmas, opts, 1);
+}
+
+int blur_gaussian_bf16_sigmas_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                               const blur_opts* opts)
+{
+    return blur_ch_sigmas_multi(m, reinterpret_cast<const ff_bf16*>(src), reinterpret_cast<ff_bf16*>(dst), nframes, rows, cols, channels, sigmas, opts, 0);
 }
 
 int blur_convolve_lines_c32_dev(blur_ctx* ctx, const float* d_in, float* d_out, int nlines, int n, const float* multipliers)

@@ -149,7 +149,7 @@ __device__ __forceinline__ void ff_quirk_cols_tile(unsigned char* scratch, float
 // One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
 template <typename T, int NKB, bool QUIRK, int CH>
 __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
-                                                  int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips)
+                                                  int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips, FwChSel chsel)
 {
     static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
     static_assert(ff_is_pixel_v<T>, "float32, u16, float16 or bfloat16 pixels");
@@ -166,7 +166,9 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
 
     const int nx = g.nxcd, xcd = blockIdx.x % nx, in_xcd = blockIdx.x / nx, per_xcd = (ntasks + nx - 1) / nx, task = xcd * per_xcd + in_xcd;
     if (in_xcd >= per_xcd || task >= ntasks) return;
-    const int c = task % CH, xc = (task / CH) % chunks, seg = (task / (CH * chunks)) % nseg, f = task / (CH * chunks * nseg);
+    // the launch's active channels (FwChSel, fw_kernels.hpp; all CH of them: c = task % CH)
+    const int nact = CH == 1 ? 1 : fw_chsel_count(chsel), c = CH == 1 ? 0 : static_cast<int>((chsel >> (4 + 2 * (task % nact))) & 3u);
+    const int xc = (task / nact) % chunks, seg = (task / (nact * chunks)) % nseg, f = task / (nact * chunks * nseg);
     const int x0 = xc * kFxChunk;
     const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
     const T* img = src + static_cast<size_t>(f) * g.rows * g.cols * CH;
@@ -490,8 +492,10 @@ __host__ __device__ constexpr bool ff_class_in_contract(int nkb) { return nkb <=
 
 template <typename T> struct FfEntryT {
     int nkb;
-    // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (float and the half types: qk.mbits always is; u16: never read)
-    hipError_t (*blur)(hipStream_t, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk, const T* strips);
+    // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (float and the half types: qk.mbits always is; u16: never read);
+    // chsel: the channels to blur
+    hipError_t (*blur)(hipStream_t, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk, const T* strips,
+                       FwChSel chsel);
 };
 using FfEntry = FfEntryT<float>;
 using FfEntryU16 = FfEntryT<uint16_t>;
@@ -499,30 +503,34 @@ using FfEntryF16 = FfEntryT<ff_f16>;
 using FfEntryBf16 = FfEntryT<ff_bf16>;
 
 template <typename T, int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int num_cus, const FfQuirk& qk,
-                                                               bool quirk, const T* strips)
+                                                               bool quirk, const T* strips, FwChSel chsel)
 {
     using C = FfCfg<NKB, ff_is_half_v<T> ? 1 : 2>;
-    const FxLaunch l = fx_plan_launch(g, CH, C::NT, num_cus);
+    const int nact = fw_chsel_count(chsel);
+    if (nact < 1 || nact > CH) return hipErrorInvalidValue;
+    for (int i = 0; i < nact; ++i)
+        if (static_cast<int>((chsel >> (4 + 2 * i)) & 3u) >= CH) return hipErrorInvalidValue;
+    const FxLaunch l = fx_plan_launch(g, nact, C::NT, num_cus);
     if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
     const hipError_t e = fx_set_lds(attr_done, C::LDS, ff_blur<T, NKB, true, CH>, ff_blur<T, NKB, false, CH>);
     if (e != hipSuccess) return e;
     if (quirk)
         hipLaunchKernelGGL((ff_blur<T, NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), qk, strips);
+                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel);
     else
         hipLaunchKernelGGL((ff_blur<T, NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), qk, strips);
+                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel);
     return hipGetLastError();
 }
 
 template <typename T, int NKB> hipError_t ff_launch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk,
-                                                    bool quirk, const T* strips)
+                                                    bool quirk, const T* strips, FwChSel chsel)
 {
-    if (ch == 1) return ff_launch_ch<T, NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
+    if (ch == 1) return ff_launch_ch<T, NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel);
     if constexpr (ff_class_ok_t<T>(NKB, 3)) {
-        if (ch == 3) return ff_launch_ch<T, NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
-        if (ch == 4) return ff_launch_ch<T, NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips);
+        if (ch == 3) return ff_launch_ch<T, NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel);
+        if (ch == 4) return ff_launch_ch<T, NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel);
     }
     return hipErrorInvalidValue;
 }

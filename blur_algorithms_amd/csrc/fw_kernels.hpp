@@ -1,6 +1,7 @@
 // fw_kernels.hpp -- the fused matrix-core kernel that gives a workgroup ONE channel of its strip: u8 images of CH = 1, 3 or 4
-// channels (grayscale, BGR, BGRA / RGBA).  CH = 1 and 4 are instantiated for every window class (NKB = 3 .. 23 blocks of 16
-// positions: pad <= 168), CH = 3 for the WIDE windows only (NKB = 13 .. 23: pad 73 .. 168; narrower BGR windows run on fx_blur_u8).
+// channels (grayscale, BGR, BGRA / RGBA), every window class (NKB = 3 .. 23 blocks of 16 positions: pad <= 168).  Whole BGR frames
+// with one sigma take CH = 3 for the WIDE windows only (NKB = 13 .. 23: pad 73 .. 168; narrower BGR windows run on fx_blur_u8); the
+// narrow CH = 3 instantiations serve the launches over a subset of the channels (one sigma per channel: FwChSel, Fw3Entry).
 //
 // fx_kernels.hpp keeps (NKB - 1) / 2 column-pass accumulator tiles per channel and a wave carries all three channels: 240 AGPRs at
 // NKB = 11 and no room beyond.  Here a workgroup handles ONE channel of its strip of 128 pixel columns -- the task list has the
@@ -21,7 +22,7 @@
 //   * stores: CH = 1 transposes a finished tile's bytes inside lane quads (fx_quad_transpose) so that a lane owns 4 adjacent pixels
 //     of one row: one dword store per lane and row group.  CH = 3 and 4 store single bytes: the output bytes of one channel are
 //     every CH-th byte of the image (the channel tasks' stores meet in L2 before the lines go to memory);
-//   * narrow windows (CH = 1, 4 only): the vector work of a step goes out over the column pass's NKB triples (the hand-off in
+//   * narrow windows: the vector work of a step goes out over the column pass's NKB triples (the hand-off in
 //     slots 0 .. 7, the emission in 1 .. 4, the staging from slot 5 on) and the stores over the row pass's first four blocks.
 //     Below NKB = 9 there are fewer slots than that: the loops run on past the products, max(NKB, 9) and max(NKB, 4) slots, the
 //     ones beyond NKB holding only vector work.
@@ -34,6 +35,28 @@
 #endif
 
 namespace blur_amd {
+
+// The channels a launch works on (blur_gaussian_*_sigmas_*: the channels that share one sigma), packed into one kernel argument
+// (uniform: it stays in scalar registers): the count n in bits 0 .. 2, the i-th active channel in bits 4 + 2 i, 5 + 2 i.  The task
+// list runs over (frame, segment, chunk, active channel); the layout's stride stays CH and the quirk's sums are indexed by the real
+// channel.  fw_chsel_all(CH) gives the task order of a launch over every channel.
+typedef uint32_t FwChSel;
+constexpr FwChSel fw_chsel_all(int ch) { return static_cast<FwChSel>(ch) | (ch > 1 ? 0xe40u : 0u); }      // channels 0, 1, 2, 3 in order
+inline FwChSel fw_chsel_mask(unsigned mask, int ch)
+{
+    FwChSel s = 0;
+    int n = 0;
+    for (int c = 0; c < ch; ++c)
+        if (mask >> c & 1u) s |= static_cast<FwChSel>(c) << (4 + 2 * n++);
+    return s | static_cast<FwChSel>(n);
+}
+__host__ __device__ constexpr int fw_chsel_count(FwChSel s) { return static_cast<int>(s & 7u); }
+inline unsigned fw_chsel_bits(FwChSel s)                                                                   // bit c: channel c is active
+{
+    unsigned m = 0;
+    for (int i = 0; i < fw_chsel_count(s); ++i) m |= 1u << ((s >> (4 + 2 * i)) & 3u);
+    return m;
+}
 
 template <int NKB> struct FwCfg {
     static constexpr int PADA = 8 * (NKB - 2), WIN = kFxChunk + 2 * PADA, GPR = WIN / 4, PER = (GPR + 7) / 8;
@@ -121,9 +144,9 @@ __device__ __forceinline__ void fc_quirk_cols_tile(unsigned char* scratch, float
 // One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
 template <int NKB, bool QUIRK, int CH>
 __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
-                                                     int chunks, int tps, int nseg, int ntasks, FwQuirk<CH> qk, const uint8_t* __restrict__ strips)
+                                                     int chunks, int tps, int nseg, int ntasks, FwQuirk<CH> qk, const uint8_t* __restrict__ strips, FwChSel chsel)
 {
-    static_assert(CH == 1 || CH == 4 || (CH == 3 && NKB >= 13), "one or four channels; three for the wide windows only (narrower: fx_blur_u8)");
+    static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
     using C = FwCfg<NKB>;
     constexpr int PADA = C::PADA, PW = C::PW, NT = C::NT, PER = C::PER;
     constexpr int RS = NKB > 4 ? NKB : 4;                         // row-pass slots: the stores of the previous tile need four
@@ -134,7 +157,9 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
 
     const int nx = g.nxcd, xcd = blockIdx.x % nx, in_xcd = blockIdx.x / nx, per_xcd = (ntasks + nx - 1) / nx, task = xcd * per_xcd + in_xcd;
     if (in_xcd >= per_xcd || task >= ntasks) return;
-    const int c = task % CH, xc = (task / CH) % chunks, seg = (task / (CH * chunks)) % nseg, f = task / (CH * chunks * nseg);
+    // the launch's active channels (FwChSel; all CH of them: c = task % CH)
+    const int nact = CH == 1 ? 1 : fw_chsel_count(chsel), c = CH == 1 ? 0 : static_cast<int>((chsel >> (4 + 2 * (task % nact))) & 3u);
+    const int xc = (task / nact) % chunks, seg = (task / (nact * chunks)) % nseg, f = task / (nact * chunks * nseg);
     const int x0 = xc * kFxChunk;
     const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
     const uint8_t* img = src + static_cast<size_t>(f) * g.rows * g.cols * CH;
@@ -475,20 +500,24 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
 }
 
 template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FwQuirk<CH>* qk,
-                                               const uint8_t* strips)
+                                               const uint8_t* strips, FwChSel chsel = fw_chsel_all(CH))
 {
     using C = FwCfg<NKB>;
-    const FxLaunch l = fx_plan_launch(g, CH, C::NT, num_cus);
+    const int nact = fw_chsel_count(chsel);
+    if (nact < 1 || nact > CH) return hipErrorInvalidValue;
+    for (int i = 0; i < nact; ++i)
+        if (static_cast<int>((chsel >> (4 + 2 * i)) & 3u) >= CH) return hipErrorInvalidValue;
+    const FxLaunch l = fx_plan_launch(g, nact, C::NT, num_cus);
     if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
     const hipError_t e = fx_set_lds(attr_done, C::LDS, fw_blur_u8<NKB, true, CH>, fw_blur_u8<NKB, false, CH>);
     if (e != hipSuccess) return e;
     if (qk)
         hipLaunchKernelGGL((fw_blur_u8<NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), *qk, strips);
+                           l.nseg, static_cast<int>(l.ntasks), *qk, strips, chsel);
     else
         hipLaunchKernelGGL((fw_blur_u8<NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), FwQuirk<CH>{}, strips);
+                           l.nseg, static_cast<int>(l.ntasks), FwQuirk<CH>{}, strips, chsel);
     return hipGetLastError();
 }
 
@@ -502,25 +531,44 @@ template <int NKB> hipError_t fw_launch_u8c3(hipStream_t st, const uint8_t* src,
 
 struct FcEntry {
     int nkb;
-    // ch: 1 or 4; qk: the quirk's sums (null: nyquist_quirk = 0)
-    hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk, const uint8_t* strips);
+    // ch: 1 or 4; qk: the quirk's sums (null: nyquist_quirk = 0); chsel: the channels to blur
+    hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk, const uint8_t* strips,
+                          FwChSel chsel);
 };
+
+// three channels, a subset of them per launch (one sigma per channel), every window class: the strips are whole windows (fx_prepass
+// with narrow = 0) and the quirk's sums fx_prepass's, as for the wide three-channel entry
+struct Fw3Entry {
+    int nkb;
+    hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk, const uint8_t* strips, FwChSel chsel);
+};
+template <int NKB> hipError_t fw_launch_u8c3_sel(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk,
+                                                 const uint8_t* strips, FwChSel chsel)
+{
+    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, chsel);
+}
 
 // the one- and four-channel entry (FcEntry; fx_registry.hpp: find_fc_entry) of every window class
 template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk,
-                                              const uint8_t* strips)
+                                              const uint8_t* strips, FwChSel chsel)
 {
-    if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips);
-    if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips);
+    if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips, chsel);
+    if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips, chsel);
     return hipErrorInvalidValue;
 }
 
-// fw_conv_<NKB>.hip: BLUR_FW(NKB) for every window class, BLUR_FW_C3(NKB) as well for the wide ones
+// fw_conv_<NKB>.hip: BLUR_FW(NKB) for every window class (one and four channels, and three for the channel-subset launches),
+// BLUR_FW_C3(NKB) as well for the wide ones (whole BGR frames)
 #define BLUR_FW(NKB_)                                                                                       \
     namespace blur_amd {                                                                                    \
     const FcEntry* fc_entry_##NKB_()                                                                        \
     {                                                                                                       \
         static const FcEntry e = { NKB_, fw_launch_u8c14<NKB_> };                                           \
+        return &e;                                                                                          \
+    }                                                                                                       \
+    const Fw3Entry* fw3_entry_##NKB_()                                                                      \
+    {                                                                                                       \
+        static const Fw3Entry e = { NKB_, fw_launch_u8c3_sel<NKB_> };                                       \
         return &e;                                                                                          \
     }                                                                                                       \
     }
@@ -561,11 +609,13 @@ __device__ __forceinline__ void fc_edge_strips_body(const uint8_t* __restrict__ 
 // The quirk's sums (FcQuirk) for a CH-channel image: workgroup (band of band_rows rows, batch of 256 G dwords of a row, frame).
 // A thread owns G dwords of every row of the band: CH = 1 four pixels, CH = 4 one pixel's four channels.  Exact integers; srow and
 // zsum must be zero before the launch (they are completed with atomics).  sred[row][channel][lane]: lane l of every wave adds
-// into slot l (fx_altsums_body).
+// into slot l (fx_altsums_body).  chmask: the channels whose sums the launch that follows reads (bit c; one sigma per channel: a
+// subset) -- the row sums of the others are neither reduced nor added up (srow and zsum stay 0 for them).
 constexpr int kFcSumRows = 32;
 template <int CH, int G>
 __device__ __forceinline__ void fc_altsums_body(const uint8_t* __restrict__ src, int* __restrict__ srow, int* __restrict__ cpart, long long* __restrict__ zsum,
-                                                int rows, int cols, int pad, int nbands, int cpitch, int band, int batch, int f, int (*sred)[CH][64], int band_rows)
+                                                int rows, int cols, int pad, int nbands, int cpitch, int band, int batch, int f, int (*sred)[CH][64], int band_rows,
+                                                unsigned chmask)
 {
     const int tid = threadIdx.x;
     const uint32_t rowbytes = static_cast<uint32_t>(cols) * CH;
@@ -618,11 +668,12 @@ __device__ __forceinline__ void fc_altsums_body(const uint8_t* __restrict__ src,
                         col[j][k] += wy * v;
                     }
 #pragma unroll
-                for (int ch = 0; ch < CH; ++ch) atomicAdd(&sred[r - rs][ch][tid & 63], s[ch]);
+                for (int ch = 0; ch < CH; ++ch)
+                    if (chmask >> ch & 1u) atomicAdd(&sred[r - rs][ch][tid & 63], s[ch]);                  // uniform
             }
         }
         __syncthreads();
-        if (tid < (re - rs) * CH) {
+        if (tid < (re - rs) * CH && (chmask >> (tid % CH) & 1u)) {
             const int rr = tid / CH, ch = tid - rr * CH;
             const int* p64 = &sred[rr][ch][0];
             int v = 0;
@@ -645,13 +696,13 @@ __device__ __forceinline__ void fc_altsums_body(const uint8_t* __restrict__ src,
 template <int CH, int G>
 __global__ __launch_bounds__(256) void fc_prepass(const uint8_t* __restrict__ src, int* __restrict__ srow, int* __restrict__ cpart, long long* __restrict__ zsum,
                                                   uint8_t* __restrict__ strips, int rows, int cols, int pad, int pada, int nbands, int nbatches, int cpitch, int n_alt,
-                                                  int chunks, int nright, int strip_blocks, int band_rows)
+                                                  int chunks, int nright, int strip_blocks, int band_rows, unsigned chmask)
 {
     __shared__ int sred[kFcSumRows][CH][64];
     int b = blockIdx.x;
     if (b < n_alt) {
         const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
-        fc_altsums_body<CH, G>(src, srow, cpart, zsum, rows, cols, pad, nbands, cpitch, band, batch, f, sred, band_rows);
+        fc_altsums_body<CH, G>(src, srow, cpart, zsum, rows, cols, pad, nbands, cpitch, band, batch, f, sred, band_rows, chmask);
     } else {
         b -= n_alt;
         const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);

@@ -410,6 +410,85 @@ int blur_gaussian_bf16_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uin
                                        double sigma, const blur_opts* opts);
 int blur_gaussian_bf16_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
                                         double sigma, const blur_opts* opts);
+/* ---- one sigma per channel ---------------------------------------------------------------------------------------------
+   The _sigmas_ entries take `const double sigmas[channels]` where the entries above take `double sigma` (a Lab or YCrCb image whose
+   luminance and colour channels want different blurs; BGRA whose alpha is to stay as it is).
+     sigmas[c] > 0   channel c of the result is, bit for bit, channel c of what the scalar entry of the same type returns for sigma =
+                     sigmas[c] with the same opts (for float32, float16 and bfloat16 the frame's power-of-two scale still comes from
+                     max|x| over the whole frame).  The one exception is u8 with three channels, where the scalar call runs other
+                     kernels (the u8c3 policy): there the channel meets the same float64 oracle under the same tie rule.
+     sigmas[c] == 0  channel c is copied bit for bit; an in-place call does not touch it.  All zeros: a copy of the batch.
+   All positive entries equal and no zero: the call IS the scalar entry (u8 with three channels: blur_gaussian_u8c3_batch_dev).
+   Otherwise the channels are grouped by sigma and opts->engine applies per group: AUTO gives a group the fused kernel wherever
+   the scalar entry's rules give it to that sigma (u8 with three channels: wherever the 1- and 4-channel rules do) and the f32
+   plane path elsewhere; FUSED fails with BLUR_ERR_UNSUPPORTED if any group has no fused kernel; FFT takes the plane path for every
+   group.  After the call blur_last_engine returns family 6 if every blurred group ran on the fused kernel and 0 otherwise, the note
+   naming the groups on the plane path.  Any overlap of source and destination, in place included, is read from one copy.
+   BLUR_ERR_INVALID: channels not in {1, 3, 4}, a NULL pointer (sigmas included), nframes < 0, rows or cols <= 0, a negative, NaN or
+   infinite sigma; BLUR_ERR_UNSUPPORTED: an entry whose pad exceeds min(rows, cols) - 1.  Every entry is checked before the device
+   is touched (ctx may then be NULL) and before anything is written; nframes == 0 is a no-op.  The f16 / bf16 entries take the
+   samples' bit patterns, as the scalar ones.  _batch_multi_: sharded by frame like the scalar calls.
+   Cost (DESIGN.md 2.5 has the measurements): the call is cheaper than what it replaces, one scalar call per distinct sigma into a
+   temporary and a gather of one channel from each, and with two or more distinct sigmas cheaper than those scalar calls alone.
+   It is NOT cheaper than one scalar call: with one distinct sigma beside zeros it costs about one scalar call (4 channels), and
+   for u8 with three channels more than one -- (0, s, s) with a narrow window (pad <= 72) takes about 1.4 times the u8c3 call
+   with s, whose kernel blurs three channels per workgroup where this path blurs one. */
+int blur_gaussian_u8_sigmas_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels,
+                                      const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u8_sigmas_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int rows, int cols, int channels,
+                                const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u8_sigmas_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, int channels,
+                                 const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u8_sigmas_batch_multi_dev(blur_multi* m, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels,
+                                            const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u8_sigmas_batch_multi_host(blur_multi* m, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, int channels,
+                                             const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f32_sigmas_batch_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels,
+                                       const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f32_sigmas_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int channels,
+                                 const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f32_sigmas_host(blur_ctx* ctx, const float* src, float* dst, int rows, int cols, int channels,
+                                  const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f32_sigmas_batch_multi_dev(blur_multi* m, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels,
+                                             const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f32_sigmas_batch_multi_host(blur_multi* m, const float* src, float* dst, int nframes, int rows, int cols, int channels,
+                                              const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u16_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                       const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u16_sigmas_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels,
+                                 const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u16_sigmas_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels,
+                                  const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u16_sigmas_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                             const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u16_sigmas_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
+                                              const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f16_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                       const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f16_sigmas_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels,
+                                 const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f16_sigmas_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels,
+                                  const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f16_sigmas_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                             const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f16_sigmas_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
+                                              const double* sigmas, const blur_opts* opts);
+int blur_gaussian_bf16_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                        const double* sigmas, const blur_opts* opts);
+int blur_gaussian_bf16_sigmas_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int rows, int cols, int channels,
+                                  const double* sigmas, const blur_opts* opts);
+int blur_gaussian_bf16_sigmas_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, int channels,
+                                   const double* sigmas, const blur_opts* opts);
+int blur_gaussian_bf16_sigmas_batch_multi_dev(blur_multi* m, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                              const double* sigmas, const blur_opts* opts);
+int blur_gaussian_bf16_sigmas_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
+                                               const double* sigmas, const blur_opts* opts);
+/* host-only plan of the calls above (no GPU needed; the same host code the entries use): for channel c, out[3 c] = its group (the
+   channels of equal sigma share an index, counted in the order of their first channel; -1 for sigma = 0), out[3 c + 1] = the pad
+   of its sigma on this frame, out[3 c + 2] = the fused kernel's window class NKB, 8 (NKB - 4) < pad <= 8 (NKB - 2), or 0 where the
+   pad has no fused kernel (pad > 168).  Status as the entries above; BLUR_ERR_INVALID also for a null `out`. */
+int blur_gaussian_sigmas_plan(int rows, int cols, int channels, const double* sigmas, int* out);
+
 /* fastboxblur over a batch, sharded by frame exactly like the two calls above, in place (blur_fastboxblur_u8_batch_dev on
    each shard); arguments and errors as blur_fastboxblur_u8_batch_dev, nframes == 0 is a no-op, shards without frames idle. */
 int blur_fastboxblur_u8_batch_multi_dev(blur_multi* m, uint8_t* d_inout, int nframes, int w, int h, int channels,

@@ -252,6 +252,41 @@ inline void gaussian_blur_bf16(uint16_t* bits, int rows, int cols, int channels,
     check(ctx, blur_gaussian_bf16_host(ctx, bits, bits, rows, cols, channels, sigma, opts), "gaussian_blur_bf16");
 }
 
+// One sigma per channel (blur_gaussian_*_sigmas_host): sigmas[channels]; channel c is blurred as the call above with sigmas[c] blurs
+// it, 0 leaves the channel as it is (Lab / YCrCb with 1-11-11: gaussian_blur(lab, sig) with double sig[3] = { 0, 11, 11 }; BGRA
+// whose alpha stays: { s, s, s, 0 }).  In place, as the scalar overloads.  (A literal 0 as the sigma argument is ambiguous between
+// these overloads and the scalar ones, int -> double and the null pointer ranking alike; neither accepts it: sigma 0 and a null
+// sigmas are both BLUR_ERR_INVALID.)
+inline void gaussian_blur(uint8_t* data, int rows, int cols, int channels, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u8_sigmas_host(ctx, data, data, rows, cols, channels, sigmas, opts), "gaussian_blur");
+}
+template <class Mat, class = decltype(std::declval<Mat&>().channels())> void gaussian_blur(Mat& image, const double* sigmas)
+{
+    gaussian_blur(reinterpret_cast<uint8_t*>(image.data), static_cast<int>(image.size[0]), static_cast<int>(image.size[1]), static_cast<int>(image.channels()), sigmas);
+}
+inline void gaussian_blur(float* data, int rows, int cols, int channels, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f32_sigmas_host(ctx, data, data, rows, cols, channels, sigmas, opts), "gaussian_blur");
+}
+inline void gaussian_blur(uint16_t* data, int rows, int cols, int channels, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u16_sigmas_host(ctx, data, data, rows, cols, channels, sigmas, opts), "gaussian_blur");
+}
+inline void gaussian_blur_f16(uint16_t* bits, int rows, int cols, int channels, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f16_sigmas_host(ctx, bits, bits, rows, cols, channels, sigmas, opts), "gaussian_blur_f16");
+}
+inline void gaussian_blur_bf16(uint16_t* bits, int rows, int cols, int channels, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_bf16_sigmas_host(ctx, bits, bits, rows, cols, channels, sigmas, opts), "gaussian_blur_bf16");
+}
+
 // pocketfft_1D(image, sigma) (Source.cpp:280-392) and pocketfft_2D(image, sigma) (Source.cpp:143-277): the two
 // pocketfft paths multiply all N/2+1 bins with the kernel's own spectrum (no Nyquist-slot quirk) and, inside the
 // cropped image, both equal the linear convolution of the reflect-101 extended image -- the engine's
