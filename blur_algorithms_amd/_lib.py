@@ -123,6 +123,26 @@ SYMBOLS = {
     "blur_gaussian_bf16_sigmas_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
     "blur_gaussian_bf16_sigmas_batch_multi_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
     "blur_gaussian_bf16_sigmas_batch_multi_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_u8_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+        C.POINTER(BlurOpts)]),
+    "blur_gaussian_u8_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_f32_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+        C.POINTER(BlurOpts)]),
+    "blur_gaussian_f32_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_u16_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+        C.POINTER(BlurOpts)]),
+    "blur_gaussian_u16_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+        C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+        C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
     "blur_gaussian_sigmas_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "blur_fastboxblur_u8_batch_multi_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "blur_fastboxblur_u8_batch_multi_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

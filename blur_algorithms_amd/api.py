@@ -177,21 +177,65 @@ def _gauss_array(image, out, dtype, batch=False):
     return a, res, shape
 
 
+def _gauss_strided_layout(shape, strides):
+    """The pitched layout of a frame tensor [rows, cols], [rows, cols, C] or [n, rows, cols, C] with these strides (in elements):
+    (row pitch, frame stride) in elements, or None where the pitched entries cannot address it.  Accepted: contiguous tensors, and
+    views with strides (frame_stride, pitch, C, 1), (pitch, C, 1) or (pitch, 1) with pitch >= cols * C and positive strides -- a
+    region of interest `frames[:, y0:y1, x0:x1, :]`, a surface with padded rows.  A slice along the channel axis, a stepped
+    slice, a flipped or permuted view is None.  (The stride of a dimension of size 1 addresses nothing and is not looked at; a
+    single frame's stride is rows * pitch then.)"""
+    shape, strides = tuple(shape), tuple(strides)
+    if len(shape) != len(strides) or len(shape) not in (2, 3, 4):
+        return None
+    if len(shape) == 2:
+        (rows, cols), ch, (pitch, sx), sc, n, fs = shape, 1, strides, 1, 1, None
+    elif len(shape) == 3:
+        (rows, cols, ch), (pitch, sx, sc), n, fs = shape, strides, 1, None
+    else:
+        (n, rows, cols, ch), (fs, pitch, sx, sc) = shape, strides
+    if (ch > 1 and sc != 1) or (cols > 1 and sx != ch):
+        return None
+    if rows > 1:
+        if pitch < cols * ch:
+            return None
+    else:
+        pitch = cols * ch
+    if n > 1:
+        if fs < (rows - 1) * pitch + cols * ch:
+            return None
+    else:
+        fs = rows * pitch
+    return pitch, fs
+
+
 def _gauss_tensor(image, out, dtype, device=None):
-    """the CUDA tensors of a per-channel Gaussian call: (source, result (default: the source), (n, rows, cols, C)).  device: frames
-    [n, rows, cols, C] on that device only"""
+    """the CUDA tensors of a per-channel Gaussian call: (source, result (default: the source), (n, rows, cols, C), layout).
+    device (BlurMulti): contiguous frames [n, rows, cols, C] on that device only, layout None.  Otherwise the source and the result
+    may each be contiguous or a pitched view (_gauss_strided_layout); layout is None when both are contiguous, else (source
+    pitch, source frame stride, result pitch, result frame stride) in BYTES"""
     import torch
     want = {np.uint8: torch.uint8, np.uint16: torch.uint16, np.float32: torch.float32, np.float16: torch.float16, BF16: torch.bfloat16}[dtype]
     t = image
-    if (not isinstance(t, torch.Tensor) or t.dtype != want or not t.is_cuda or not t.is_contiguous()
+    sl = None
+    if isinstance(t, torch.Tensor) and device is None:
+        sl = _gauss_strided_layout(t.shape, t.stride())
+    if (not isinstance(t, torch.Tensor) or t.dtype != want or not t.is_cuda or not (t.is_contiguous() or sl is not None)
             or (device is not None and (t.dim() != 4 or t.device.index != device))):
         layout = "[rows, cols], [rows, cols, C] or [n, rows, cols, C]" if device is None else "[n, rows, cols, C] on devices[0]"
-        raise ValueError("expected a contiguous CUDA %s tensor %s" % (_dtype_name(dtype), layout))
+        raise ValueError("expected a contiguous CUDA %s tensor %s%s" % (_dtype_name(dtype), layout, ", or a view of one with whole pixels in rows "
+                                                                         "a pitch apart (a region of interest, padded rows)" if device is None else ""))
     shape = _gauss_frames_shape(tuple(t.shape))
     dst = t if out is None else out
-    if not isinstance(dst, torch.Tensor) or dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda or not dst.is_contiguous():
+    dl = None
+    if isinstance(dst, torch.Tensor) and device is None:
+        dl = _gauss_strided_layout(dst.shape, dst.stride())
+    if (not isinstance(dst, torch.Tensor) or dst.shape != t.shape or dst.dtype != t.dtype or not dst.is_cuda
+            or not (dst.is_contiguous() or dl is not None)):
         raise ValueError("out must match the input")
-    return t, dst, shape
+    if device is not None or (t.is_contiguous() and dst.is_contiguous()):
+        return t, dst, shape, None
+    es = t.element_size()
+    return t, dst, shape, (sl[0] * es, sl[1] * es, dl[0] * es, dl[1] * es)
 
 
 def _is_sigma_sequence(sigma):
@@ -566,6 +610,12 @@ class BlurContext:
 
         torch CUDA tensor: asynchronous on torch's current stream, returns `out` (default: in place, like pffft_).  numpy array:
         host round trip, returns a new array.
+
+        The CUDA tensor, and `out` independently, may be a pitched view instead of a contiguous tensor: a region of interest
+        `frames[:, y0:y1, x0:x1, :]`, a surface whose rows are padded (strides (frame_stride, pitch, C, 1), (pitch, C, 1) or
+        (pitch, 1), pitch >= cols * C).  Nothing is repacked and nothing outside the view is written; `out=None` blurs the view in
+        place.  Channel slices, stepped, flipped or permuted views raise ValueError.  The same holds for gaussian_f32, gaussian_u16,
+        gaussian_f16 and gaussian_bf16; BlurMulti takes contiguous frames only.
         """
         return self._gaussian(image, sigma, out, nyquist_quirk, engine, np.uint8, "u8")
 
@@ -623,9 +673,13 @@ class BlurContext:
             for f in range(n):
                 self._check(host_entry(self._h, a.ctypes.data + f * fb, res.ctypes.data + f * fb, rows, cols, ch, sg, C.byref(o)))
             return _gauss_result(res, out, dtype)
-        t, dst, (n, rows, cols, ch) = _gauss_tensor(image, out, dtype)
+        t, dst, (n, rows, cols, ch), lay = _gauss_tensor(image, out, dtype)
         sg = _sigma_arg(sigma, ch, t.dim() == 2)
         self.use_torch_stream()
+        if lay is not None:           # a pitched view on either side (blur_gaussian_<tname>[_sigmas]_pitched_batch_dev): nothing is repacked
+            pitched_entry = getattr(self._lib, "blur_gaussian_%s%s_pitched_batch_dev" % (tname, mid))
+            self._check(pitched_entry(self._h, t.data_ptr(), lay[0], lay[1], dst.data_ptr(), lay[2], lay[3], n, rows, cols, ch, sg, C.byref(o)))
+            return dst
         batch_dev_entry = getattr(self._lib, "blur_gaussian_%s%s_batch_dev" % (tname, mid))
         self._check(batch_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, sg, C.byref(o)))
         return dst
@@ -753,7 +807,7 @@ class BlurMulti:
             self._check(multi_host_entry(self._h, a.ctypes.data, res.ctypes.data, n, rows, cols, ch, _sigma_arg(sigma, ch), C.byref(o)))
             return _gauss_result(res, out, dtype)
         import torch
-        t, dst, (n, rows, cols, ch) = _gauss_tensor(frames, out, dtype, device=self.devices[0])
+        t, dst, (n, rows, cols, ch), _ = _gauss_tensor(frames, out, dtype, device=self.devices[0])
         torch.cuda.synchronize(t.device)
         multi_dev_entry = getattr(self._lib, "blur_gaussian_%s%s_batch_multi_dev" % (tname, mid))
         self._check(multi_dev_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, _sigma_arg(sigma, ch), C.byref(o)))

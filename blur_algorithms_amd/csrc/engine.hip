@@ -1737,12 +1737,34 @@ static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
     return BLUR_OK;
 }
 
+// Where the rows and frames of a per-channel call lie, in bytes (blur_gaussian_*_pitched_batch_dev; the packed entries: ch_packed).
+// Row r of frame f of the source starts at f sframe + r spitch, of the destination at f dframe + r dpitch.
+struct ChLayout {
+    size_t spitch, sframe, dpitch, dframe;
+};
+static ChLayout ch_packed(int rows, int cols, int ch, size_t es)
+{
+    const size_t pitch = static_cast<size_t>(cols) * ch * es;
+    return ChLayout{ pitch, pitch * rows, pitch, pitch * rows };
+}
+// the bytes from a frame's first to behind its last
+static size_t ch_frame_span(int rows, size_t pitch, size_t rowbytes) { return static_cast<size_t>(rows - 1) * pitch + rowbytes; }
+// the fused kernels' view of a layout (choose_ch_engine has checked that a frame's span fits 32-bit offsets)
+static FwPitch fw_pitch_of(const ChLayout& L)
+{
+    return FwPitch{ static_cast<uint32_t>(L.spitch), static_cast<uint32_t>(L.dpitch), L.sframe, L.dframe };
+}
+
+static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump, FwChSel chsel,
+                       const ChLayout* lay);
+
 // the fused kernel for CH = 1, 4 (fw_kernels.hpp): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
 // Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).
 // chsel: the channels to blur (blur_ch_sigmas_batch_impl: one sigma per channel); the pre-pass reads every channel (a pixel is one
 // dword) and completes the quirk's row sums of these channels only
-static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel)
+static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel, const ChLayout& L)
 {
+    const FwPitch pt = fw_pitch_of(L);
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
     const FcEntry* fe = find_fc_entry(nkb);
     if (!fe) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for 1 / 4 channels: no kernel instantiated for this pad");
@@ -1784,11 +1806,11 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
         auto kern = ch == 1 ? (G == 1 ? fc_prepass<1, 1> : (G == 2 ? fc_prepass<1, 2> : fc_prepass<1, 4>))
                             : (G == 1 ? fc_prepass<4, 1> : (G == 2 ? fc_prepass<4, 2> : fc_prepass<4, 4>));
         hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, p.sz.pad, pada, nbands,
-                           nbatches, cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel));
+                           nbatches, cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel), pt.src_pitch, pt.src_frame);
         HIP_TRY(ctx, hipGetLastError());
     }
     TimedLaunch t(ctx, 0, nframes);
-    HIP_TRY(ctx, fe->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel));
+    HIP_TRY(ctx, fe->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel, pt));
     return BLUR_OK;
 }
 
@@ -1798,8 +1820,9 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
 // T = float, uint16_t, ff_f16 or ff_bf16.  u16: no max|x| (the scale is a constant of the call), and without the quirk no sums at
 // all; the half types: as float.  chsel: the channels to blur (the pre-pass covers every channel either way: max|x| is the frame's).
 template <typename T>
-static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel)
+static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel, const ChLayout& L)
 {
+    const FwPitch pt = fw_pitch_of(L);
     constexpr bool u16 = std::is_same_v<T, uint16_t>;
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
     const FfEntryT<T>* fe = find_ff_entry_t<T>(nkb);
@@ -1851,7 +1874,7 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
                                        : pick(ff_prepass<T, 4, 1>, ff_prepass<T, 4, 2>, ff_prepass<T, 4, 4>));
         if (n_alt + n_strip > 0)
             hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, mbits, spart, cpart, strips, rows, cols, p.sz.pad, pada, nbands,
-                               nbatches, ne, n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0);
+                               nbatches, ne, n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0, pt.src_pitch, pt.src_frame);
         HIP_TRY(ctx, hipGetLastError());
         if (quirk) {
             auto fin = ch == 1 ? ff_finalize<1> : (ch == 3 ? ff_finalize<3> : ff_finalize<4>);
@@ -1860,7 +1883,7 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
         }
     }
     TimedLaunch t(ctx, 0, nframes);
-    HIP_TRY(ctx, fe->blur(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, strips, chsel));
+    HIP_TRY(ctx, fe->blur(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, strips, chsel, pt));
     return BLUR_OK;
 }
 
@@ -1876,12 +1899,26 @@ template <typename T> __device__ __forceinline__ float chan_widen(T v)
     else return static_cast<float>(v);
 }
 
+// These kernels walk a frame by rows (blockIdx.y, gridDim.y apart) and by pixels of a row (the x dimension): `pitch` is the row
+// pitch of the interleaved frame in bytes (a packed frame: cols ch sizeof(T)); the planes are packed.
+template <typename T> __device__ __forceinline__ const T* chan_row(const T* base, size_t r, size_t pitch)
+{
+    return reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(base) + r * pitch);
+}
+template <typename T> __device__ __forceinline__ T* chan_row(T* base, size_t r, size_t pitch)
+{
+    return reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(base) + r * pitch);
+}
+
 template <typename T>
-__global__ void chan_maxabs(const T* __restrict__ src, unsigned* __restrict__ mbits, size_t n)
+__global__ void chan_maxabs(const T* __restrict__ src, unsigned* __restrict__ mbits, int rows, int cols, int ch, size_t pitch)
 {
     unsigned m = 0;
-    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        m = max(m, __float_as_uint(chan_widen(src[i])) & 0x7fffffffu);
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        const T* line = chan_row(src, r, pitch);
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cols * ch; i += gridDim.x * blockDim.x)
+            m = max(m, __float_as_uint(chan_widen(line[i])) & 0x7fffffffu);
+    }
     if (m) atomicMax(mbits, m);
 }
 
@@ -1895,41 +1932,54 @@ __device__ inline int chan_scale_exp(unsigned mbits)
 }
 
 template <typename T>
-__global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes, size_t px, int ch, const unsigned* __restrict__ mbits, unsigned mask)
+__global__ void chan_split(const T* __restrict__ src, float* __restrict__ planes, int rows, int cols, int ch, const unsigned* __restrict__ mbits, unsigned mask,
+                           size_t pitch)
 {
     float scale = 1.f;
     if constexpr (std::is_same_v<T, float> || ff_is_half_v<T>) scale = ldexpf(1.f, chan_scale_exp(*mbits));
-    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        for (int c = 0; c < ch; ++c) {
-            if (!(mask >> c & 1u)) continue;
-            if constexpr (std::is_same_v<T, float>) planes[c * px + i] = src[i * ch + c] * scale;
-            else if constexpr (ff_is_half_v<T>) planes[c * px + i] = chan_widen(src[i * ch + c]) * scale;
-            else planes[c * px + i] = static_cast<float>(src[i * ch + c]);
-        }
+    const size_t px = static_cast<size_t>(rows) * cols;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        const T* line = chan_row(src, r, pitch);
+        float* prow = planes + static_cast<size_t>(r) * cols;
+        for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < cols; x += gridDim.x * blockDim.x)
+            for (int c = 0; c < ch; ++c) {
+                if (!(mask >> c & 1u)) continue;
+                if constexpr (std::is_same_v<T, float>) prow[c * px + x] = line[x * ch + c] * scale;
+                else if constexpr (ff_is_half_v<T>) prow[c * px + x] = chan_widen(line[x * ch + c]) * scale;
+                else prow[c * px + x] = static_cast<float>(line[x * ch + c]);
+            }
+    }
 }
 
 template <typename T>
-__global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst, size_t px, int ch, const unsigned* __restrict__ mbits, unsigned mask)
+__global__ void chan_pack(const float* __restrict__ planes, T* __restrict__ dst, int rows, int cols, int ch, const unsigned* __restrict__ mbits, unsigned mask,
+                          size_t pitch)
 {
     float unscale = 1.f;
     if constexpr (std::is_same_v<T, float> || ff_is_half_v<T>) unscale = ldexpf(1.f, -chan_scale_exp(*mbits));
-    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < px; i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        for (int c = 0; c < ch; ++c) {
-            if (!(mask >> c & 1u)) continue;
-            if constexpr (std::is_same_v<T, uint8_t>)  // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
-                dst[i * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffu);
-            else if constexpr (std::is_same_v<T, uint16_t>)  // the same rule 16 bits wide: truncate, keep the low 16 bits
-                dst[i * ch + c] = static_cast<uint16_t>(static_cast<uint32_t>(static_cast<int>(planes[c * px + i] + 0.5f)) & 0xffffu);
-            else if constexpr (ff_is_half_v<T>)             // one rounding to nearest even (binary16: overflow to +-Inf)
-                dst[i * ch + c] = T{ ff_half_round<T>(planes[c * px + i] * unscale) };
-            else
-                dst[i * ch + c] = planes[c * px + i] * unscale;
-        }
+    const size_t px = static_cast<size_t>(rows) * cols;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        T* line = chan_row(dst, r, pitch);                   // (only samples x < cols of a row are written)
+        const float* prow = planes + static_cast<size_t>(r) * cols;
+        for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < cols; x += gridDim.x * blockDim.x)
+            for (int c = 0; c < ch; ++c) {
+                if (!(mask >> c & 1u)) continue;
+                if constexpr (std::is_same_v<T, uint8_t>)  // (uint8_t)(v + 0.5f) of the reference (Utils.hpp:189,204-206): truncate, keep the low byte
+                    line[x * ch + c] = static_cast<uint8_t>(static_cast<uint32_t>(static_cast<int>(prow[c * px + x] + 0.5f)) & 0xffu);
+                else if constexpr (std::is_same_v<T, uint16_t>)  // the same rule 16 bits wide: truncate, keep the low 16 bits
+                    line[x * ch + c] = static_cast<uint16_t>(static_cast<uint32_t>(static_cast<int>(prow[c * px + x] + 0.5f)) & 0xffffu);
+                else if constexpr (ff_is_half_v<T>)             // one rounding to nearest even (binary16: overflow to +-Inf)
+                    line[x * ch + c] = T{ ff_half_round<T>(prow[c * px + x] * unscale) };
+                else
+                    line[x * ch + c] = prow[c * px + x] * unscale;
+            }
+    }
 }
 
 // mask: the channels to blur (one sigma per channel: the others are neither split nor packed; max|x| is the whole frame's either way)
 template <typename T>
-static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts, unsigned mask = 0xfu)
+static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, double sigma, const blur_opts* opts, const ChLayout& L,
+                      unsigned mask = 0xfu)
 {
     Prepared p;
     if (int rc = prepare(ctx, rows, cols, sigma, opts, p, false)) return rc;
@@ -1937,16 +1987,18 @@ static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int 
     if (int rc = ensure_work(ctx, px * sizeof(float))) return rc;
     if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_planes), &ctx->ch_planes_bytes, px * ch * sizeof(float) + 16)) return rc;
     unsigned* mbits = reinterpret_cast<unsigned*>(ctx->ch_planes + px * ch);          // behind the planes
-    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((px + 255) / 256, 4096));
+    // (as many workgroups as before the kernels walked rows: about 4096, a row's pixels in x and the rows in y)
+    const unsigned bx = static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(cols) + 255) / 256, 4096));
+    const dim3 blocks(bx, static_cast<unsigned>(std::min<size_t>(rows, std::max<size_t>(1, 4096 / bx))));
     for (int f = 0; f < nframes; ++f) {
-        const T* s = d_src + static_cast<size_t>(f) * px * ch;
-        T* d = d_dst + static_cast<size_t>(f) * px * ch;
+        const T* s = reinterpret_cast<const T*>(reinterpret_cast<const char*>(d_src) + static_cast<size_t>(f) * L.sframe);
+        T* d = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f) * L.dframe);
         if constexpr (std::is_same_v<T, float> || ff_is_half_v<T>) {
             HIP_TRY(ctx, hipMemsetAsync(mbits, 0, sizeof(unsigned), ctx->stream));
-            hipLaunchKernelGGL(chan_maxabs<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, mbits, px * ch);
+            hipLaunchKernelGGL(chan_maxabs<T>, blocks, dim3(256), 0, ctx->stream, s, mbits, rows, cols, ch, L.spitch);
             HIP_TRY(ctx, hipGetLastError());
         }
-        hipLaunchKernelGGL(chan_split<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->ch_planes, px, ch, mbits, mask);
+        hipLaunchKernelGGL(chan_split<T>, blocks, dim3(256), 0, ctx->stream, s, ctx->ch_planes, rows, cols, ch, mbits, mask, L.spitch);
         HIP_TRY(ctx, hipGetLastError());
         for (int c = 0; c < ch; ++c) {
             if (!(mask >> c & 1u)) continue;
@@ -1954,7 +2006,7 @@ static int run_planes(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int 
             if (int rc = launch_rowpass<float, 1>(ctx, plane, ctx->work, rows, cols, p.sz.pad, *p.row, p.m_row)) return rc;
             if (int rc = launch_colpass<float, 1>(ctx, ctx->work, plane, rows, cols, p.sz.pad, *p.col, p.m_col, p.col_group)) return rc;
         }
-        hipLaunchKernelGGL(chan_pack<T>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ch_planes, d, px, ch, mbits, mask);
+        hipLaunchKernelGGL(chan_pack<T>, blocks, dim3(256), 0, ctx->stream, ctx->ch_planes, d, rows, cols, ch, mbits, mask, L.dpitch);
         HIP_TRY(ctx, hipGetLastError());
     }
     return BLUR_OK;
@@ -1972,10 +2024,74 @@ static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nf
     return ctx ? BLUR_OK : BLUR_ERR_INVALID;
 }
 
+// the arguments a pitched entry adds (blur_gaussian_*_pitched_batch_dev), without the device: pitches and frame strides in bytes
+static int check_ch_layout(blur_ctx* ctx, int nframes, int rows, int cols, int channels, size_t es, const ChLayout& L)
+{
+    if (rows <= 0 || cols <= 0 || (channels != 1 && channels != 3 && channels != 4)) return BLUR_OK;       // (refused by the other checks)
+    const size_t rowbytes = static_cast<size_t>(cols) * channels * es;
+    if (L.spitch < rowbytes || L.dpitch < rowbytes) return fail(ctx, BLUR_ERR_INVALID, "row pitch below cols * channels * sizeof(element)");
+    if (L.spitch % es || L.dpitch % es || L.sframe % es || L.dframe % es)
+        return fail(ctx, BLUR_ERR_INVALID, "row pitch and frame stride must be multiples of the element size");
+    if (nframes > 1 && (L.sframe < ch_frame_span(rows, L.spitch, rowbytes) || L.dframe < ch_frame_span(rows, L.dpitch, rowbytes)))
+        return fail(ctx, BLUR_ERR_INVALID, "frame stride below (rows - 1) * pitch + cols * channels * sizeof(element): the frames of the batch would overlap");
+    return BLUR_OK;
+}
+
+// Overlapping calls read from a packed copy.  The byte spans [base, base + (n - 1) frame + (rows - 1) pitch + rowbytes) of the source
+// and the destination are compared: an in-place call and two rectangles of one parent image both intersect.  ch_gather_rows moves
+// the source rectangles into the workspace in one launch (V: 16, 4 or 1 bytes per thread, by what the addresses allow).
+template <typename V>
+__global__ __launch_bounds__(256) void ch_gather_rows(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int rows, size_t rowbytes, size_t spitch,
+                                                      size_t sframe)
+{
+    const size_t nv = rowbytes / sizeof(V);
+    const unsigned char* s = src + blockIdx.z * sframe;
+    unsigned char* d = dst + blockIdx.z * static_cast<size_t>(rows) * rowbytes;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        const V* sl = reinterpret_cast<const V*>(s + static_cast<size_t>(r) * spitch);
+        V* dl = reinterpret_cast<V*>(d + static_cast<size_t>(r) * rowbytes);
+        for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < nv; i += static_cast<size_t>(gridDim.x) * blockDim.x) dl[i] = sl[i];
+    }
+}
+
+static bool ch_spans_overlap(const void* src, const void* dst, int nframes, int rows, size_t rowbytes, const ChLayout& L)
+{
+    const char* s0 = static_cast<const char*>(src);
+    const char* d0 = static_cast<const char*>(dst);
+    const size_t sspan = static_cast<size_t>(nframes - 1) * L.sframe + ch_frame_span(rows, L.spitch, rowbytes);
+    const size_t dspan = static_cast<size_t>(nframes - 1) * L.dframe + ch_frame_span(rows, L.dpitch, rowbytes);
+    return s0 < d0 + dspan && d0 < s0 + sspan;
+}
+
+// the source rectangles -> ctx->ch_copy, packed; *src and the layout's source side then describe the copy
+template <typename T>
+static int ch_copy_source(blur_ctx* ctx, const T** src, int nframes, int rows, size_t rowbytes, ChLayout& L)
+{
+    const size_t fb = rowbytes * rows;
+    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
+    if (L.spitch == rowbytes && (nframes == 1 || L.sframe == fb)) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, *src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(*src) | L.spitch | L.sframe | rowbytes | reinterpret_cast<uintptr_t>(ctx->ch_copy);
+        const size_t vb = (bits & 15) == 0 ? 16 : ((bits & 3) == 0 ? 4 : 1);
+        const unsigned bx = static_cast<unsigned>(std::min<size_t>((rowbytes / vb + 255) / 256, 64));
+        const dim3 grid(bx, static_cast<unsigned>(std::min<size_t>(rows, 1024)), static_cast<unsigned>(nframes));
+        auto kern = vb == 16 ? ch_gather_rows<uint4> : (vb == 4 ? ch_gather_rows<uint32_t> : ch_gather_rows<unsigned char>);
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const unsigned char*>(*src), reinterpret_cast<unsigned char*>(ctx->ch_copy), rows,
+                           rowbytes, L.spitch, L.sframe);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    *src = reinterpret_cast<const T*>(ctx->ch_copy);
+    L.spitch = rowbytes;
+    L.sframe = fb;
+    return BLUR_OK;
+}
+
 // The engine of a per-channel blur with one sigma (blur_ch_batch_impl; blur_ch_sigmas_batch_impl: of a group of channels): p.fx set =
 // the fused kernel, else the plane fallback, and `note` says why.  choice: AUTO, FUSED or FFT.
 template <typename T>
-static int choose_ch_engine(blur_ctx* ctx, int rows, int cols, int channels, double sigma, const blur_opts* opts, int choice, Prepared& p, std::string& note)
+static int choose_ch_engine(blur_ctx* ctx, int rows, int cols, int channels, double sigma, const blur_opts* opts, int choice, Prepared& p, std::string& note,
+                            const ChLayout& L)
 {
     constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;
     // The fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED: a kernel for the pad, the frame and quirk limits; a
@@ -2000,8 +2116,9 @@ static int choose_ch_engine(blur_ctx* ctx, int rows, int cols, int channels, dou
             why = half ? "fused kernel for float16 / bfloat16 images: pad 105 .. 168 is outside the library's own choice, as for float32; ask for it with engine = FUSED"
                   : u16 ? "fused kernel for u16 images: pad 105 .. 168 exceeds 1e-6 of full scale on full-scale content (1.2e-6); ask for it with engine = FUSED"
                       : "fused kernel for float32 images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED";
-        else if (p.fx && static_cast<long long>(rows) * cols * channels * static_cast<long long>(sizeof(T)) > 0xfffff000ll)
-            why = "fused matrix-core engine: frame too large for 32-bit offsets";
+        else if (p.fx && std::max(ch_frame_span(rows, L.spitch, static_cast<size_t>(cols) * channels * sizeof(T)),
+                                  ch_frame_span(rows, L.dpitch, static_cast<size_t>(cols) * channels * sizeof(T))) > 0xfffff000ull)
+            why = "fused matrix-core engine: frame too large for 32-bit offsets";       // (a pitched frame: its span, (rows - 1) pitch + a row's bytes)
         if (why) {
             if (choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, why);
             p.fx = nullptr;
@@ -2016,13 +2133,20 @@ static int choose_ch_engine(blur_ctx* ctx, int rows, int cols, int channels, dou
 // 1e-6 of full scale is 0.066 of a grey level); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 / run_ff<T>)
 // and the engine error's text
 template <typename T>
-static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts,
+                              const ChLayout* lay = nullptr)
 {
     constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;      // ffk: the ff_kernels.hpp types
+    // lay: the pitched entries' layout (null: packed frames).  Three u8 channels, packed: the u8c3 entry and its kernels; pitched:
+    // fw_blur_u8<NKB, Q, 3> over the three channels (Fw3Entry), the route of the one-sigma-per-channel calls
+    if (lay)
+        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay)) return rc;
     if (int rc = check_ch_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma)) return rc;
     if constexpr (u8) {
-        if (channels == 3) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
+        if (channels == 3 && !lay) return blur_gaussian_u8c3_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, sigma, opts);
     }
+    ChLayout L = lay ? *lay : ch_packed(rows, cols, channels, sizeof(T));
+    if (nframes == 1) L.sframe = L.dframe = 0;               // (not used; in-place calls compare the layouts)
     const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
     if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
         return fail(ctx, BLUR_ERR_UNSUPPORTED, half ? (std::string(ch_type_name<T>()) + " images: engine must be AUTO, FUSED or FFT").c_str()
@@ -2030,41 +2154,38 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
                                                            : (ffk ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT")));
     Prepared p;
     std::string note;
-    if (int rc = choose_ch_engine<T>(ctx, rows, cols, channels, sigma, opts, choice, p, note)) return rc;
+    if (int rc = choose_ch_engine<T>(ctx, rows, cols, channels, sigma, opts, choice, p, note, L)) return rc;
     if (nframes == 0) return BLUR_OK;
-    const size_t fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(T);
-    // overlap of the source and destination ranges (over the whole batch): the fused kernel reads its neighbours' pixels while it
-    // writes, and the plane path writes frame f before it reads frame f + 1.  An in-place call of the plane path needs no copy
-    // (frame f is read whole before it is written); every other overlap reads from a copy
-    const char* lo = reinterpret_cast<const char*>(d_src < d_dst ? d_src : d_dst);
-    const char* hi = reinterpret_cast<const char*>(d_src < d_dst ? d_dst : d_src);
-    const bool overlap = static_cast<size_t>(hi - lo) < fb * nframes;
-    if (overlap && (p.fx || d_src != d_dst)) {
-        if (d_src == d_dst) {       // in place: in parts of at most 1 GiB (a part's result never touches a later part's source)
+    const size_t rowbytes = static_cast<size_t>(cols) * channels * sizeof(T), fb = rowbytes * rows;
+    // overlap of the source and destination spans (over the whole batch; pitched frames: ch_spans_overlap): the fused kernel reads
+    // its neighbours' pixels while it writes, and the plane path writes frame f before it reads frame f + 1.  An in-place call of
+    // the plane path needs no copy (frame f is read whole before it is written); every other overlap reads from a copy
+    const bool in_place = d_src == d_dst && L.spitch == L.dpitch && L.sframe == L.dframe;
+    if (ch_spans_overlap(d_src, d_dst, nframes, rows, rowbytes, L) && (p.fx || !in_place)) {
+        if (in_place) {             // in parts of at most 1 GiB (a part's result never touches a later part's source)
             const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
             if (static_cast<size_t>(nframes) > cap) {
                 for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
                     const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
-                    T* part = d_dst + static_cast<size_t>(f0) * fe;
-                    if (int rc = blur_ch_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts)) return rc;
+                    T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * L.dframe);
+                    if (int rc = blur_ch_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts, lay)) return rc;
                 }
                 return BLUR_OK;
             }
         }
-        if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
-        d_src = reinterpret_cast<const T*>(ctx->ch_copy);
+        if (int rc = ch_copy_source(ctx, &d_src, nframes, rows, rowbytes, L)) return rc;
     }
     if (p.fx) {
         ctx->last_family = 6;
-        if constexpr (ffk) return run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels));
-        else return run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels));
+        if constexpr (ffk) return run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels), L);
+        else return channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, nframes, rows, cols, p, nullptr, fw_chsel_all(3), &L)
+                                  : run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels), L);
     }
     blur_opts o;
     blur_opts_default(&o);
     if (opts) o = *opts;
     o.engine = BLUR_ENGINE_FFT;
-    if (int rc = run_planes(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, &o)) return rc;
+    if (int rc = run_planes(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, &o, L)) return rc;
     ctx->last_family = 0;
     ctx->engine_note = note;
     return BLUR_OK;
@@ -2093,8 +2214,6 @@ static int blur_ch_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols,
 // One sigma per channel (blur_gaussian_{u8,f32,u16,f16,bf16}_sigmas_*): channel c is what the scalar entry returns for sigmas[c];
 // sigma = 0 leaves the channel as it is
 // ======================================================================================
-static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump, FwChSel chsel);
-
 // The channels of a call by sigma: group g holds the channels in mask[g] with sigma[g] > 0, in the order of their first channel;
 // zero_mask: the channels with sigma = 0
 struct SigmaGroups {
@@ -2157,6 +2276,33 @@ __global__ __launch_bounds__(256) void chan_copy(const uint8_t* __restrict__ src
         if (mask >> static_cast<unsigned>(e % CH) & 1u) reinterpret_cast<E*>(dst)[e] = reinterpret_cast<const E*>(src)[e];
 }
 
+// the same for pitched frames, row by row: only the masked channels' samples of the rows' cols pixels are written (frames in z)
+template <int ES>
+__global__ __launch_bounds__(256) void chan_copy_rows(const uint8_t* __restrict__ src, uint8_t* dst, int rows, int cols, int ch, unsigned mask, ChLayout L)
+{
+    using E = std::conditional_t<ES == 1, uint8_t, std::conditional_t<ES == 2, uint16_t, uint32_t>>;
+    const uint8_t* s = src + blockIdx.z * L.sframe;
+    uint8_t* d = dst + blockIdx.z * L.dframe;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        const E* sl = reinterpret_cast<const E*>(s + static_cast<size_t>(r) * L.spitch);
+        E* dl = reinterpret_cast<E*>(d + static_cast<size_t>(r) * L.dpitch);
+        for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < cols * ch; e += gridDim.x * blockDim.x)
+            if (mask >> static_cast<unsigned>(e % ch) & 1u) dl[e] = sl[e];
+    }
+}
+
+template <typename T>
+static int launch_chan_copy_rows(blur_ctx* ctx, const T* src, T* dst, int nframes, int rows, int cols, int ch, unsigned mask, const ChLayout& L)
+{
+    if (!mask || nframes == 0) return BLUR_OK;
+    const unsigned bx = static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(cols) * ch + 255) / 256, 64));
+    const dim3 grid(bx, static_cast<unsigned>(std::min<size_t>(rows, 1024)), static_cast<unsigned>(nframes));
+    hipLaunchKernelGGL(chan_copy_rows<sizeof(T)>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), rows, cols, ch,
+                       mask, L);
+    HIP_TRY(ctx, hipGetLastError());
+    return BLUR_OK;
+}
+
 template <typename T>
 static int launch_chan_copy(blur_ctx* ctx, const T* src, T* dst, size_t nelem, int ch, unsigned mask)
 {
@@ -2180,12 +2326,17 @@ static int launch_chan_copy(blur_ctx* ctx, const T* src, T* dst, size_t nelem, i
 // the strips are as wide as the pad: both belong to the group) and the fused launch over the group's channels, or the plane path
 // over them.  The strips and sums workspaces are reused from group to group.
 template <typename T>
-static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts,
+                                     const ChLayout* lay = nullptr)
 {
     constexpr bool u8 = std::is_same_v<T, uint8_t>;
     SigmaGroups sg;
+    if (lay)
+        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay)) return rc;
     if (int rc = check_ch_sigmas_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, sg)) return rc;
-    if (sg.ngroups == 1 && !sg.zero_mask) return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[0], opts);
+    if (sg.ngroups == 1 && !sg.zero_mask) return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[0], opts, lay);
+    ChLayout L = lay ? *lay : ch_packed(rows, cols, channels, sizeof(T));
+    if (nframes == 1) L.sframe = L.dframe = 0;
     const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
     if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
         return fail(ctx, BLUR_ERR_UNSUPPORTED, (std::string(ch_type_name<T>()) + " images, one sigma per channel: engine must be AUTO, FUSED or FFT").c_str());
@@ -2193,32 +2344,31 @@ static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, in
     Prepared p[4];
     std::string why[4];
     for (int g = 0; g < sg.ngroups; ++g)
-        if (int rc = choose_ch_engine<T>(ctx, rows, cols, channels, sg.sigma[g], opts, choice, p[g], why[g])) return rc;
+        if (int rc = choose_ch_engine<T>(ctx, rows, cols, channels, sg.sigma[g], opts, choice, p[g], why[g], L)) return rc;
     ctx->engine_note.clear();
     if (nframes == 0) return BLUR_OK;
-    const bool in_place = d_src == d_dst;
+    const bool in_place = d_src == d_dst && L.spitch == L.dpitch && L.sframe == L.dframe;
     if (in_place && sg.ngroups == 0) return BLUR_OK;            // every channel is left as it is
-    const size_t fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(T);
-    const char* lo = reinterpret_cast<const char*>(d_src < d_dst ? d_src : d_dst);
-    const char* hi = reinterpret_cast<const char*>(d_src < d_dst ? d_dst : d_src);
-    if (static_cast<size_t>(hi - lo) < fb * nframes) {
+    const size_t rowbytes = static_cast<size_t>(cols) * channels * sizeof(T), fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(T);
+    const bool packed = L.spitch == rowbytes && L.dpitch == rowbytes && (nframes == 1 || (L.sframe == fb && L.dframe == fb));
+    if (ch_spans_overlap(d_src, d_dst, nframes, rows, rowbytes, L)) {
         if (in_place) {             // in parts of at most 1 GiB (a part's result never touches a later part's source)
             const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
             if (static_cast<size_t>(nframes) > cap) {
                 for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
                     const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
-                    T* part = d_dst + static_cast<size_t>(f0) * fe;
-                    if (int rc = blur_ch_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas, opts)) return rc;
+                    T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * L.dframe);
+                    if (int rc = blur_ch_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas, opts, lay)) return rc;
                 }
                 return BLUR_OK;
             }
         }
-        if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
-        d_src = reinterpret_cast<const T*>(ctx->ch_copy);
+        if (int rc = ch_copy_source(ctx, &d_src, nframes, rows, rowbytes, L)) return rc;
     }
     if (!in_place) {
-        if (sg.ngroups == 0) HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (!packed) {                  // a pitched destination: the samples of the sigma = 0 channels only, row by row
+            if (int rc = launch_chan_copy_rows<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.zero_mask, L)) return rc;
+        } else if (sg.ngroups == 0) HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
         else if (int rc = launch_chan_copy<T>(ctx, d_src, d_dst, fe * nframes, channels, sg.zero_mask)) return rc;       // (every other channel is written below)
     }
     blur_opts fft_opts;
@@ -2230,12 +2380,12 @@ static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, in
         if (p[g].fx) {
             const FwChSel chsel = fw_chsel_mask(sg.mask[g], channels);
             int rc;
-            if constexpr (!u8) rc = run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], chsel);
-            else rc = channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, nframes, rows, cols, p[g], nullptr, chsel)
-                                    : run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], chsel);
+            if constexpr (!u8) rc = run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], chsel, L);
+            else rc = channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, nframes, rows, cols, p[g], nullptr, chsel, &L)
+                                    : run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], chsel, L);
             if (rc) return rc;
         } else {
-            if (int rc = run_planes(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[g], &fft_opts, sg.mask[g])) return rc;
+            if (int rc = run_planes(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[g], &fft_opts, L, sg.mask[g])) return rc;
             char head[96];
             std::snprintf(head, sizeof head, "%ssigma %g (channel mask 0x%x) on the plane path: ", note.empty() ? "" : "; ", sg.sigma[g], sg.mask[g]);
             note += head + why[g];
@@ -2539,14 +2689,18 @@ static int run_mx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
 // both passes in one kernel on the matrix cores (fx_kernels.hpp): no intermediate in memory
 // chsel != 0 (blur_ch_sigmas_batch_impl: one sigma per channel): only these channels, on the one-channel-per-workgroup kernel of
 // the window class (Fw3Entry: whole-window strips)
-static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump = nullptr, FwChSel chsel = 0)
+// lay (with chsel only; null: packed frames): the caller's layout, source and destination already disjoint
+static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump = nullptr, FwChSel chsel = 0,
+                       const ChLayout* lay = nullptr)
 {
     const size_t px = static_cast<size_t>(rows) * cols;
+    if (lay && !chsel) return fail(ctx, BLUR_ERR_INVALID, "run_fx_u8c3: a layout goes with a channel selection");
+    const FwPitch pt = lay ? fw_pitch_of(*lay) : fw_pitch_packed(rows, cols, 3, 1);
     // in place (the reference's own calling convention, Source.cpp:429,567): a strip reads its neighbours' columns and the rows
     // below while they are being written, so the frames are read from a copy in the workspace
     const uint8_t* lo = d_src < d_dst ? d_src : d_dst;
     const uint8_t* hi = d_src < d_dst ? d_dst : d_src;
-    if (static_cast<size_t>(hi - lo) < px * 3 * nframes) {
+    if (!lay && static_cast<size_t>(hi - lo) < px * 3 * nframes) {
         // (a large batch: in parts of at most 1 GiB, the cap of every engine's workspace -- frames are disjoint, so a part's result
         // never touches a later part's source)
         const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / (px * 3));
@@ -2597,7 +2751,7 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
     if (!p.mx_quirk) {
         TimedLaunch t(ctx, 1, nframes);
         hipLaunchKernelGGL(fx_prepass<1>, dim3(n_strip), dim3(256), 0, ctx->stream, d_src, nullptr, nullptr, nullptr, ctx->fx_strips, rows, cols, p.sz.pad, pada, 1, 1, 0, chunks_x,
-                           g.nright, strip_blocks, kFxSumRows, narrow);
+                           g.nright, strip_blocks, kFxSumRows, narrow, pt.src_pitch, pt.src_frame);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (p.mx_quirk) {
@@ -2622,7 +2776,7 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
           const int n_alt = nbands * nbatches * nframes;
           auto kern = gpt == 1 ? fx_prepass<1> : (gpt == 2 ? fx_prepass<2> : fx_prepass<4>);
           hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zpart, ctx->fx_strips, rows, cols, p.sz.pad, pada, nbands,
-                             nbatches, n_alt, chunks_x, g.nright, strip_blocks, band_rows, narrow);
+                             nbatches, n_alt, chunks_x, g.nright, strip_blocks, band_rows, narrow, pt.src_pitch, pt.src_frame);
           HIP_TRY(ctx, hipGetLastError()); }
         qk.srow_part = srow;
         qk.cpart = cpart;
@@ -2644,7 +2798,7 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
         const Fw3Entry* fe3 = find_fw3_entry(nkb);
         if (!fe3 || vdump || stamps) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for a subset of three channels: no kernel instantiated for this pad");
         TimedLaunch t(ctx, 0, nframes);
-        HIP_TRY(ctx, fe3->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel));
+        HIP_TRY(ctx, fe3->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel, pt));
         return BLUR_OK;
     }
     { TimedLaunch t(ctx, 0, nframes);
@@ -2723,7 +2877,8 @@ static int run_wr_tiled(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int
         if (p.tl_quirk) {
             TimedLaunch t(ctx, 1, 1);
             const int n_alt = nbands * nbatches;
-            hipLaunchKernelGGL(fx_prepass<1>, dim3(n_alt), dim3(256), 0, ctx->stream, src, srow, cpart, zpart, nullptr, rows, cols, pad, 0, nbands, nbatches, n_alt, 1, 0, 1, band_rows, 0);
+            hipLaunchKernelGGL(fx_prepass<1>, dim3(n_alt), dim3(256), 0, ctx->stream, src, srow, cpart, zpart, nullptr, rows, cols, pad, 0, nbands, nbatches, n_alt, 1, 0, 1, band_rows, 0,
+                               static_cast<uint32_t>(cols) * 3u, static_cast<size_t>(rows) * cols * 3);
             HIP_TRY(ctx, hipGetLastError());
             const int ne = (pitch + 255) / 256, nh = (rows + 255) / 256;
             const size_t lds = (static_cast<size_t>(3) * (256 + 2 * pad) + (2 * pad + 1) + 3 + 3 * 256) * sizeof(double);
@@ -3789,6 +3944,77 @@ int blur_gaussian_sigmas_plan(int rows, int cols, int channels, const double* si
         out[3 * c + 2] = fe ? fe->nkb : 0;
     }
     return BLUR_OK;
+}
+
+// pitched frames and regions of interest (blur_amd.h: blur_gaussian_*_pitched_batch_dev): pitches and frame strides in bytes
+int blur_gaussian_u8_pitched_batch_dev(blur_ctx* ctx, const uint8_t* d_src, size_t src_pitch, size_t src_frame_stride, uint8_t* d_dst, size_t dst_pitch,
+                                       size_t dst_frame_stride, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, &L);
+}
+
+int blur_gaussian_u8_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint8_t* d_src, size_t src_pitch, size_t src_frame_stride, uint8_t* d_dst, size_t dst_pitch,
+                                              size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_f32_pitched_batch_dev(blur_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst, size_t dst_pitch,
+                                        size_t dst_frame_stride, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, &L);
+}
+
+int blur_gaussian_f32_sigmas_pitched_batch_dev(blur_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst, size_t dst_pitch,
+                                               size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_u16_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                                        size_t dst_frame_stride, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, opts, &L);
+}
+
+int blur_gaussian_u16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                                               size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_f16_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                                        size_t dst_frame_stride, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_batch_impl(ctx, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), nframes, rows, cols, channels, sigma, opts, &L);
+}
+
+int blur_gaussian_f16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                                               size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_bf16_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                                         size_t dst_frame_stride, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigma, opts, &L);
+}
+
+int blur_gaussian_bf16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                                                size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigmas, opts, &L);
 }
 
 // u8 images, one sigma per channel

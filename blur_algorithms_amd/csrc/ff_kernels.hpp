@@ -149,7 +149,7 @@ __device__ __forceinline__ void ff_quirk_cols_tile(unsigned char* scratch, float
 // One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
 template <typename T, int NKB, bool QUIRK, int CH>
 __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
-                                                  int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips, FwChSel chsel)
+                                                  int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips, FwChSel chsel, FwPitch pt)
 {
     static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
     static_assert(ff_is_pixel_v<T>, "float32, u16, float16 or bfloat16 pixels");
@@ -171,8 +171,9 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
     const int xc = (task / nact) % chunks, seg = (task / (nact * chunks)) % nseg, f = task / (nact * chunks * nseg);
     const int x0 = xc * kFxChunk;
     const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
-    const T* img = src + static_cast<size_t>(f) * g.rows * g.cols * CH;
-    T* out = dst + static_cast<size_t>(f) * g.rows * g.cols * CH;
+    // (FwPitch, fw_kernels.hpp: pitches and frame strides in bytes, multiples of the sample's size)
+    const T* img = reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(src) + static_cast<size_t>(f) * pt.src_frame);
+    T* out = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(dst) + static_cast<size_t>(f) * pt.dst_frame);
 
     // the frame's scale (ff_scale_exp): s = 2^e on the staged values, 2^-e on the results (u16: from the type's range, mbits is not read)
     const int sexp = U16 ? ff_scale_exp(65535.f, qk.bscale) : ff_scale_exp(__uint_as_float(qk.mbits[f]), qk.bscale);
@@ -215,10 +216,10 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
     constexpr int NLEFT = fx_left_strips(PADA);
     const int sidx = xc < NLEFT ? xc : (xc >= chunks - g.nright ? NLEFT + xc - (chunks - g.nright) : -1);      // uniform
     // byte offsets: a frame's bytes fit 32 bits (the engine's frame limit)
-    const uint32_t pitch = sidx >= 0 ? static_cast<uint32_t>(ES * CH * C::WIN) : ES * CH * static_cast<uint32_t>(g.cols);
+    const uint32_t pitch = sidx >= 0 ? static_cast<uint32_t>(ES * CH * C::WIN) : pt.src_pitch;
     const T* wbase = sidx >= 0 ? strips + (static_cast<size_t>(f) * (NLEFT + g.nright) + sidx) * g.rows * (CH * C::WIN) : img + CH * (x0 - PADA);
     const uint32_t wbytes = sidx >= 0 ? static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(ES * CH * C::WIN)
-                                      : (static_cast<uint32_t>(g.rows) * g.cols - static_cast<uint32_t>(x0 - PADA)) * static_cast<uint32_t>(ES * CH);
+                                      : static_cast<uint32_t>(g.rows - 1) * pt.src_pitch + static_cast<uint32_t>(g.cols - (x0 - PADA)) * static_cast<uint32_t>(ES * CH);
     const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wbase), 0, wbytes, kMxRsrcWord3);
     const int srow = 8 * (tid >> 6) + ((tid >> 4) & 3) + 4 * ((tid >> 3) & 1), g0 = tid & 7;      // (fx_kernels.hpp: the staging map)
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
@@ -364,13 +365,18 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
         }
     };
     // E + F: rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column of the finished tile -> f32 (16-bit types: rounded), stored at once.  Buffer
-    // stores: rows past the image, pixels right of it and tiles that do not exist get an offset outside the resource
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows) * g.cols * static_cast<uint32_t>(ES * CH), kMxRsrcWord3);
-    const uint32_t rowstep = ES * static_cast<uint32_t>(g.cols) * CH;
+    // stores: rows past the image, pixels right of it (an explicit x < cols: the bytes between two rows of a pitched frame lie inside
+    // the resource) and tiles that do not exist get an offset outside the resource
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows - 1) * pt.dst_pitch + static_cast<uint32_t>(g.cols) * (ES * CH), kMxRsrcWord3);
+    // (the pitch and the store group's row as values the compiler cannot see through: fw_kernels.hpp, store_group)
+    uint32_t rowstep_ = pt.dst_pitch;
+    asm volatile("" : "+s"(rowstep_));
+    const uint32_t rowstep = rowstep_;
     const int xcol = x0 + 32 * wave + m;
     auto emit_store = [&](int tile, bool valid, int gq) __attribute__((always_inline)) {
-        const int row0 = 32 * tile + 8 * gq + 4 * h;
-        const uint32_t base = ES * ((static_cast<uint32_t>(row0) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c));
+        int row0 = 32 * tile + 8 * gq + 4 * h;
+        asm volatile("" : "+v"(row0));
+        const uint32_t base = static_cast<uint32_t>(row0) * rowstep + ES * (static_cast<uint32_t>(xcol) * CH + static_cast<uint32_t>(c));
         if constexpr (W16) {
             uint32_t u[4];
 #pragma unroll
@@ -493,9 +499,9 @@ __host__ __device__ constexpr bool ff_class_in_contract(int nkb) { return nkb <=
 template <typename T> struct FfEntryT {
     int nkb;
     // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (float and the half types: qk.mbits always is; u16: never read);
-    // chsel: the channels to blur
+    // chsel: the channels to blur; pt: where the rows and frames lie (FwPitch)
     hipError_t (*blur)(hipStream_t, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk, const T* strips,
-                       FwChSel chsel);
+                       FwChSel chsel, FwPitch pt);
 };
 using FfEntry = FfEntryT<float>;
 using FfEntryU16 = FfEntryT<uint16_t>;
@@ -503,7 +509,7 @@ using FfEntryF16 = FfEntryT<ff_f16>;
 using FfEntryBf16 = FfEntryT<ff_bf16>;
 
 template <typename T, int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int num_cus, const FfQuirk& qk,
-                                                               bool quirk, const T* strips, FwChSel chsel)
+                                                               bool quirk, const T* strips, FwChSel chsel, FwPitch pt)
 {
     using C = FfCfg<NKB, ff_is_half_v<T> ? 1 : 2>;
     const int nact = fw_chsel_count(chsel);
@@ -517,20 +523,20 @@ template <typename T, int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, c
     if (e != hipSuccess) return e;
     if (quirk)
         hipLaunchKernelGGL((ff_blur<T, NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel);
+                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel, pt);
     else
         hipLaunchKernelGGL((ff_blur<T, NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel);
+                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel, pt);
     return hipGetLastError();
 }
 
 template <typename T, int NKB> hipError_t ff_launch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk,
-                                                    bool quirk, const T* strips, FwChSel chsel)
+                                                    bool quirk, const T* strips, FwChSel chsel, FwPitch pt)
 {
-    if (ch == 1) return ff_launch_ch<T, NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel);
+    if (ch == 1) return ff_launch_ch<T, NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt);
     if constexpr (ff_class_ok_t<T>(NKB, 3)) {
-        if (ch == 3) return ff_launch_ch<T, NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel);
-        if (ch == 4) return ff_launch_ch<T, NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel);
+        if (ch == 3) return ff_launch_ch<T, NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt);
+        if (ch == 4) return ff_launch_ch<T, NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt);
     }
     return hipErrorInvalidValue;
 }
@@ -577,7 +583,7 @@ template <typename T, int NKB> hipError_t ff_launch(hipStream_t st, const T* src
 // one sample.
 template <typename T, int CH>
 __device__ __forceinline__ void ff_edge_strips_body(const T* __restrict__ src, T* __restrict__ strips, int rows, int cols, int pada, int chunks,
-                                                    int nright, int bx, int sidx, int f)
+                                                    int nright, int bx, int sidx, int f, uint32_t spitch, size_t sframe)
 {
     const int win = kFxChunk + 2 * pada, fpr = CH * win;                // samples per strip row
     const int nleft = fx_left_strips(pada);
@@ -585,7 +591,7 @@ __device__ __forceinline__ void ff_edge_strips_body(const T* __restrict__ src, T
     const int i = bx * 256 + threadIdx.x;
     if (i >= rows * fpr) return;
     const int r = i / fpr, e = i - r * fpr, p = e / CH, ch = e - p * CH;
-    const T* line = src + (static_cast<size_t>(f) * rows + r) * cols * CH;
+    const T* line = reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(src) + static_cast<size_t>(f) * sframe + static_cast<size_t>(r) * spitch);
     strips[((static_cast<size_t>(f) * (nleft + nright) + sidx) * rows + r) * fpr + e] = line[CH * mx_refl(x0 - pada + p, cols) + ch];
 }
 
@@ -594,7 +600,8 @@ __device__ __forceinline__ void ff_edge_strips_body(const T* __restrict__ src, T
 // channel t mod CH.  Always: max|x| of the frame into mbits (integer atomicMax on the bits: order-free).  With `sums`: the parts of
 // Srow per batch (spart[f][batch][row][CH]) and the column sums per band (cpart), f32 products summed in double, every sum in a
 // fixed order.  u16 samples: no max (mbits is not touched); the sums hold integers below 2^53, exact in any order.  float16 /
-// bfloat16 samples: widened to f32 (exact), then as float samples.
+// bfloat16 samples: widened to f32 (exact), then as float samples.  spitch, sframe: the source's row pitch and frame stride in bytes
+// (FwPitch); the outputs stay packed and the partition depends on rows, cols and CH only.
 constexpr int kFfSumRows = 16;
 __host__ __device__ constexpr int ff_batch_stride(int ch) { return ch == 3 ? 255 : 256; }
 inline int ff_groups_per_thread(int cols, int ch)
@@ -605,7 +612,8 @@ inline int ff_groups_per_thread(int cols, int ch)
 
 template <typename T, int CH, int G>
 __device__ __forceinline__ void ff_altsums_body(const T* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
-                                                int rows, int cols, int pad, int nbands, int nbatches, int cpitch, int band, int batch, int f, int band_rows, bool sums)
+                                                int rows, int cols, int pad, int nbands, int nbatches, int cpitch, int band, int batch, int f, int band_rows, bool sums,
+                                                uint32_t spitch, size_t sframe)
 {
     constexpr int BS = ff_batch_stride(CH);
     constexpr bool U16 = std::is_same_v<T, uint16_t>;
@@ -617,8 +625,9 @@ __device__ __forceinline__ void ff_altsums_body(const T* __restrict__ src, unsig
     __shared__ float wmax[4];
     const int tid = threadIdx.x;
     const uint32_t ne = static_cast<uint32_t>(cols) * CH;
-    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(src + static_cast<size_t>(f) * rows * ne), 0,
-                                                                          static_cast<uint32_t>(rows) * ne * static_cast<uint32_t>(sizeof(T)), kMxRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(src) + static_cast<size_t>(f) * sframe), 0,
+        static_cast<uint32_t>(rows - 1) * spitch + ne * static_cast<uint32_t>(sizeof(T)), kMxRsrcWord3);
     const int r0 = band * band_rows, r1 = min(r0 + band_rows, rows);
     int dj[G], wx[G];
     bool own[G];
@@ -638,10 +647,10 @@ __device__ __forceinline__ void ff_altsums_body(const T* __restrict__ src, unsig
             float v[G];
 #pragma unroll
             for (int j = 0; j < G; ++j) {
-                if constexpr (U16) v[j] = static_cast<float>(__builtin_amdgcn_raw_buffer_load_b16(rimg, own[j] ? 2u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
+                if constexpr (U16) v[j] = static_cast<float>(__builtin_amdgcn_raw_buffer_load_b16(rimg, own[j] ? static_cast<uint32_t>(r) * spitch + 2u * dj[j] : 0xfffffff0u, 0, 0));
                 else if constexpr (ff_is_half_v<T>)
-                    v[j] = ff_half_widen<T>(__builtin_amdgcn_raw_buffer_load_b16(rimg, own[j] ? 2u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
-                else v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rimg, own[j] ? 4u * (static_cast<uint32_t>(r) * ne + dj[j]) : 0xfffffff0u, 0, 0));
+                    v[j] = ff_half_widen<T>(__builtin_amdgcn_raw_buffer_load_b16(rimg, own[j] ? static_cast<uint32_t>(r) * spitch + 2u * dj[j] : 0xfffffff0u, 0, 0));
+                else v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rimg, own[j] ? static_cast<uint32_t>(r) * spitch + 4u * dj[j] : 0xfffffff0u, 0, 0));
             }
             if constexpr (!U16) {
 #pragma unroll
@@ -709,16 +718,16 @@ __device__ __forceinline__ void ff_altsums_body(const T* __restrict__ src, unsig
 template <typename T, int CH, int G>
 __global__ __launch_bounds__(256) void ff_prepass(const T* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
                                                   T* __restrict__ strips, int rows, int cols, int pad, int pada, int nbands, int nbatches, int cpitch, int n_alt,
-                                                  int chunks, int nright, int strip_blocks, int band_rows, int sums)
+                                                  int chunks, int nright, int strip_blocks, int band_rows, int sums, uint32_t spitch, size_t sframe)
 {
     int b = blockIdx.x;
     if (b < n_alt) {
         const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
-        ff_altsums_body<T, CH, G>(src, mbits, spart, cpart, rows, cols, pad, nbands, nbatches, cpitch, band, batch, f, band_rows, sums != 0);
+        ff_altsums_body<T, CH, G>(src, mbits, spart, cpart, rows, cols, pad, nbands, nbatches, cpitch, band, batch, f, band_rows, sums != 0, spitch, sframe);
     } else {
         b -= n_alt;
         const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);
-        ff_edge_strips_body<T, CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f);
+        ff_edge_strips_body<T, CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f, spitch, sframe);
     }
 }
 

@@ -58,6 +58,22 @@ inline unsigned fw_chsel_bits(FwChSel s)                                        
     return m;
 }
 
+// Where the rows and the frames of a launch lie, in bytes (fw_blur_u8, ff_blur and their pre-passes): row r of frame f of the
+// source starts at f src_frame + r src_pitch, of the destination at f dst_frame + r dst_pitch.  A packed frame has pitch = cols CH
+// ES and frame = rows pitch; a pitched surface or a region of interest inside a larger image has more.  The pitches go into the
+// 32-bit offsets of the buffer resources (a frame's span, (rows - 1) pitch + cols CH ES, fits them), the frame strides into the
+// 64-bit base.  The bytes between two rows lie INSIDE the resources: loads may return them (they land where the next row's bytes
+// land in a packed frame: in padding, or under a weight of 0), stores are masked by x < cols and never reach them.
+struct FwPitch {
+    uint32_t src_pitch, dst_pitch;
+    size_t src_frame, dst_frame;
+};
+inline FwPitch fw_pitch_packed(int rows, int cols, int ch, int es)
+{
+    const uint32_t pitch = static_cast<uint32_t>(cols) * static_cast<uint32_t>(ch * es);
+    return FwPitch{ pitch, pitch, static_cast<size_t>(rows) * pitch, static_cast<size_t>(rows) * pitch };
+}
+
 template <int NKB> struct FwCfg {
     static constexpr int PADA = 8 * (NKB - 2), WIN = kFxChunk + 2 * PADA, GPR = WIN / 4, PER = (GPR + 7) / 8;
     // halfs per LDS row of the window: every thread commits PER groups of 4 positions, 32 apart, without a lane mask (fx_kernels.hpp:
@@ -144,7 +160,7 @@ __device__ __forceinline__ void fc_quirk_cols_tile(unsigned char* scratch, float
 // One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
 template <int NKB, bool QUIRK, int CH>
 __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
-                                                     int chunks, int tps, int nseg, int ntasks, FwQuirk<CH> qk, const uint8_t* __restrict__ strips, FwChSel chsel)
+                                                     int chunks, int tps, int nseg, int ntasks, FwQuirk<CH> qk, const uint8_t* __restrict__ strips, FwChSel chsel, FwPitch pt)
 {
     static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
     using C = FwCfg<NKB>;
@@ -162,8 +178,8 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
     const int xc = (task / nact) % chunks, seg = (task / (nact * chunks)) % nseg, f = task / (nact * chunks * nseg);
     const int x0 = xc * kFxChunk;
     const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
-    const uint8_t* img = src + static_cast<size_t>(f) * g.rows * g.cols * CH;
-    uint8_t* out = dst + static_cast<size_t>(f) * g.rows * g.cols * CH;
+    const uint8_t* img = src + static_cast<size_t>(f) * pt.src_frame;
+    uint8_t* out = dst + static_cast<size_t>(f) * pt.dst_frame;
 
     // fragments: hi halves in registers; of the lo halves the first TLR in registers too, the rest in LDS (the row pass reads a
     // window fragment per block already: with every lo half from LDS as well its two products would wait for the LDS pipe)
@@ -212,10 +228,10 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
     // the window's source: the image, or (edge chunks) a strip with the mirrored pixels in place -- as in fx_kernels.hpp
     constexpr int NLEFT = fx_left_strips(PADA);                // two chunks at the left edge once the window is wider than a chunk either side
     const int sidx = xc < NLEFT ? xc : (xc >= chunks - g.nright ? NLEFT + xc - (chunks - g.nright) : -1);      // uniform
-    const uint32_t pitch = sidx >= 0 ? static_cast<uint32_t>(CH * C::WIN) : static_cast<uint32_t>(CH) * static_cast<uint32_t>(g.cols);
+    const uint32_t pitch = sidx >= 0 ? static_cast<uint32_t>(CH * C::WIN) : pt.src_pitch;
     const uint8_t* wbase = sidx >= 0 ? strips + (static_cast<size_t>(f) * (NLEFT + g.nright) + sidx) * g.rows * (CH * C::WIN) : img + CH * (x0 - PADA);
     const uint32_t wbytes = sidx >= 0 ? static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(CH * C::WIN)
-                                      : (static_cast<uint32_t>(g.rows) * g.cols - static_cast<uint32_t>(x0 - PADA)) * static_cast<uint32_t>(CH);
+                                      : static_cast<uint32_t>(g.rows - 1) * pt.src_pitch + static_cast<uint32_t>(g.cols - (x0 - PADA)) * static_cast<uint32_t>(CH);
     const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(wbase), 0, wbytes, kMxRsrcWord3);
     const int srow = 8 * (tid >> 6) + ((tid >> 4) & 3) + 4 * ((tid >> 3) & 1), g0 = tid & 7;      // (fx_kernels.hpp: the staging map)
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
@@ -402,14 +418,19 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    // F: the finished tile's bytes.  Buffer stores: rows past the image, pixels right of it and tiles that do not exist get an
-    // offset outside the resource
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows) * g.cols * static_cast<uint32_t>(CH), kMxRsrcWord3);
+    // F: the finished tile's bytes.  Buffer stores: rows past the image, pixels right of it (an explicit x < cols: the bytes between
+    // two rows of a pitched frame lie inside the resource) and tiles that do not exist get an offset outside the resource
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, static_cast<uint32_t>(g.rows - 1) * pt.dst_pitch + static_cast<uint32_t>(g.cols) * CH, kMxRsrcWord3);
     const int xcol = x0 + 32 * wave + m;                                  // CH = 3, 4: the lane's pixel column
     // CH = 3: byte c of the lane's pixel in row 4 h (the stores add the row group's offset to it; CH = 4 computes each offset whole.
     // The two spellings keep each kernel's code as it was tuned: either one in the other kernel changes its registers and schedule)
-    const uint32_t lane_out = CH == 3 ? (static_cast<uint32_t>(4 * h) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c) : 0u;
-    const uint32_t rowstep = static_cast<uint32_t>(g.cols) * CH;
+    const uint32_t lane_out = CH == 3 ? static_cast<uint32_t>(4 * h) * pt.dst_pitch + static_cast<uint32_t>(xcol) * CH + static_cast<uint32_t>(c) : 0u;
+    // (the pitch as a value the compiler cannot see through, and below the row of a CH = 4 store group likewise: with a plain scalar
+    // pitch it splits every store offset into a per-step scalar and per-lane parts that it keeps in registers across the whole step
+    // loop -- 80 to 95 more registers at NKB 7 .. 11, parked in AGPRs -- where the packed kernels multiplied by cols CH in place)
+    uint32_t rowstep_ = pt.dst_pitch;
+    asm volatile("" : "+s"(rowstep_));
+    const uint32_t rowstep = rowstep_;
     const int xq = x0 + 32 * wave + 4 * (m >> 2), q = m & 3;                // CH = 1: first pixel of the lane's quad, its row in the row group
     const bool ragged = (g.cols & 3) != 0;                                // (uniform) CH = 1: the quad cut by the right edge leaves as bytes
     const int qn = xq >= g.cols ? 0 : min(4, g.cols - xq);                // pixels of the lane's quad inside the image
@@ -426,9 +447,10 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
                     __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(v >> (8 * k)), rout, rok && qn < 4 && k < qn ? o + k : 0xfffffff0u, 0, 0);
             }
         } else {                                                          // byte c of every pixel, rows 8 gq + 4 h + k of the lane's column
-            const int row0 = 32 * tile + 8 * gq + 4 * h;
+            int row0 = 32 * tile + 8 * gq + 4 * h;
+            if constexpr (CH == 4) asm volatile("" : "+v"(row0));
             const uint32_t base = CH == 3 ? lane_out + static_cast<uint32_t>(32 * tile + 8 * gq) * rowstep
-                                          : (static_cast<uint32_t>(row0) * g.cols + static_cast<uint32_t>(xcol)) * CH + static_cast<uint32_t>(c);
+                                          : static_cast<uint32_t>(row0) * rowstep + static_cast<uint32_t>(xcol) * CH + static_cast<uint32_t>(c);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const bool ok = valid && xcol < g.cols && row0 + k < g.rows;
@@ -500,7 +522,7 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
 }
 
 template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FwQuirk<CH>* qk,
-                                               const uint8_t* strips, FwChSel chsel = fw_chsel_all(CH))
+                                               const uint8_t* strips, FwChSel chsel, FwPitch pt)
 {
     using C = FwCfg<NKB>;
     const int nact = fw_chsel_count(chsel);
@@ -514,10 +536,10 @@ template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* s
     if (e != hipSuccess) return e;
     if (qk)
         hipLaunchKernelGGL((fw_blur_u8<NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), *qk, strips, chsel);
+                           l.nseg, static_cast<int>(l.ntasks), *qk, strips, chsel, pt);
     else
         hipLaunchKernelGGL((fw_blur_u8<NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), FwQuirk<CH>{}, strips, chsel);
+                           l.nseg, static_cast<int>(l.ntasks), FwQuirk<CH>{}, strips, chsel, pt);
     return hipGetLastError();
 }
 
@@ -526,34 +548,35 @@ template <int NKB> hipError_t fw_launch_u8c3(hipStream_t st, const uint8_t* src,
                                              const uint8_t* strips, float* vdump, unsigned long long* stamps)
 {
     if (vdump || stamps) return hipErrorNotSupported;            // the row-pass dump and the phase stamps are builds of fx_blur_u8 only
-    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips);
+    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, fw_chsel_all(3), fw_pitch_packed(g.rows, g.cols, 3, 1));
 }
 
 struct FcEntry {
     int nkb;
-    // ch: 1 or 4; qk: the quirk's sums (null: nyquist_quirk = 0); chsel: the channels to blur
+    // ch: 1 or 4; qk: the quirk's sums (null: nyquist_quirk = 0); chsel: the channels to blur; pt: where the rows and frames lie
     hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk, const uint8_t* strips,
-                          FwChSel chsel);
+                          FwChSel chsel, FwPitch pt);
 };
 
 // three channels, a subset of them per launch (one sigma per channel), every window class: the strips are whole windows (fx_prepass
 // with narrow = 0) and the quirk's sums fx_prepass's, as for the wide three-channel entry
 struct Fw3Entry {
     int nkb;
-    hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk, const uint8_t* strips, FwChSel chsel);
+    hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk, const uint8_t* strips, FwChSel chsel,
+                          FwPitch pt);
 };
 template <int NKB> hipError_t fw_launch_u8c3_sel(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk,
-                                                 const uint8_t* strips, FwChSel chsel)
+                                                 const uint8_t* strips, FwChSel chsel, FwPitch pt)
 {
-    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, chsel);
+    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt);
 }
 
 // the one- and four-channel entry (FcEntry; fx_registry.hpp: find_fc_entry) of every window class
 template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk,
-                                              const uint8_t* strips, FwChSel chsel)
+                                              const uint8_t* strips, FwChSel chsel, FwPitch pt)
 {
-    if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips, chsel);
-    if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips, chsel);
+    if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt);
+    if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt);
     return hipErrorInvalidValue;
 }
 
@@ -586,7 +609,7 @@ template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src
 // CH channels; the CH-channel kernel reads the whole window of an edge chunk from its strip).  A thread writes one dword.
 template <int CH>
 __device__ __forceinline__ void fc_edge_strips_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ strips, int rows, int cols, int pada, int chunks,
-                                                    int nright, int bx, int sidx, int f)
+                                                    int nright, int bx, int sidx, int f, uint32_t spitch, size_t sframe)
 {
     const int win = kFxChunk + 2 * pada, dpr = CH * win / 4;            // dwords per strip row (win is a multiple of 4)
     const int nleft = fx_left_strips(pada);
@@ -594,7 +617,7 @@ __device__ __forceinline__ void fc_edge_strips_body(const uint8_t* __restrict__ 
     const int i = bx * 256 + threadIdx.x;
     if (i >= rows * dpr) return;
     const int r = i / dpr, d = i - r * dpr;
-    const uint8_t* line = src + (static_cast<size_t>(f) * rows + r) * cols * CH;
+    const uint8_t* line = src + static_cast<size_t>(f) * sframe + static_cast<size_t>(r) * spitch;
     uint32_t o = 0;
     const int X = x0 - pada + (CH == 1 ? 4 * d : d);                   // first pixel of the dword's window position
     if (CH == 4) o = *reinterpret_cast<const uint32_t*>(line + 4 * mx_refl(X, cols));
@@ -611,19 +634,21 @@ __device__ __forceinline__ void fc_edge_strips_body(const uint8_t* __restrict__ 
 // zsum must be zero before the launch (they are completed with atomics).  sred[row][channel][lane]: lane l of every wave adds
 // into slot l (fx_altsums_body).  chmask: the channels whose sums the launch that follows reads (bit c; one sigma per channel: a
 // subset) -- the row sums of the others are neither reduced nor added up (srow and zsum stay 0 for them).
+// spitch, sframe: the source's row pitch and frame stride in bytes (FwPitch); every output stays packed and the partition depends
+// on rows, cols and CH only, so a pitched frame gives the sums of its packed copy.
 constexpr int kFcSumRows = 32;
 template <int CH, int G>
 __device__ __forceinline__ void fc_altsums_body(const uint8_t* __restrict__ src, int* __restrict__ srow, int* __restrict__ cpart, long long* __restrict__ zsum,
                                                 int rows, int cols, int pad, int nbands, int cpitch, int band, int batch, int f, int (*sred)[CH][64], int band_rows,
-                                                unsigned chmask)
+                                                unsigned chmask, uint32_t spitch, size_t sframe)
 {
     const int tid = threadIdx.x;
     const uint32_t rowbytes = static_cast<uint32_t>(cols) * CH;
-    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src + static_cast<size_t>(f) * rows * rowbytes), 0,
-                                                                          static_cast<uint32_t>(rows) * rowbytes, kMxRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src + static_cast<size_t>(f) * sframe), 0,
+                                                                          static_cast<uint32_t>(rows - 1) * spitch + rowbytes, kMxRsrcWord3);
     const int ndw = static_cast<int>((rowbytes + 3) / 4), r0 = band * band_rows, r1 = min(r0 + band_rows, rows);
     // a row that is no multiple of 4 bytes (cols * CH >= 4): its last dword is loaded `over` bytes early and shifted down, so that no
-    // load reaches past the row (the last row's would leave the buffer resource, which returns 0 for the WHOLE dword)
+    // load reaches past the row's cols CH bytes (the last row's would leave the buffer resource, which returns 0 for the WHOLE dword)
     const int over = 4 * ndw - static_cast<int>(rowbytes);
     int dj[G], wx[G][4], col[G][4], back[G];
 #pragma unroll
@@ -646,7 +671,7 @@ __device__ __forceinline__ void fc_altsums_body(const uint8_t* __restrict__ src,
             uint32_t d[RB][G];
 #pragma unroll
             for (int i = 0; i < RB; ++i) {
-                const uint32_t roff = static_cast<uint32_t>(min(rb + i, re - 1)) * rowbytes;
+                const uint32_t roff = static_cast<uint32_t>(min(rb + i, re - 1)) * spitch;
 #pragma unroll
                 for (int j = 0; j < G; ++j)
                     d[i][j] = __builtin_amdgcn_raw_buffer_load_b32(rimg, dj[j] < ndw ? roff + 4u * dj[j] - back[j] : 0xfffffff0u, 0, 0) >> (8 * back[j]);
@@ -696,17 +721,17 @@ __device__ __forceinline__ void fc_altsums_body(const uint8_t* __restrict__ src,
 template <int CH, int G>
 __global__ __launch_bounds__(256) void fc_prepass(const uint8_t* __restrict__ src, int* __restrict__ srow, int* __restrict__ cpart, long long* __restrict__ zsum,
                                                   uint8_t* __restrict__ strips, int rows, int cols, int pad, int pada, int nbands, int nbatches, int cpitch, int n_alt,
-                                                  int chunks, int nright, int strip_blocks, int band_rows, unsigned chmask)
+                                                  int chunks, int nright, int strip_blocks, int band_rows, unsigned chmask, uint32_t spitch, size_t sframe)
 {
     __shared__ int sred[kFcSumRows][CH][64];
     int b = blockIdx.x;
     if (b < n_alt) {
         const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
-        fc_altsums_body<CH, G>(src, srow, cpart, zsum, rows, cols, pad, nbands, cpitch, band, batch, f, sred, band_rows, chmask);
+        fc_altsums_body<CH, G>(src, srow, cpart, zsum, rows, cols, pad, nbands, cpitch, band, batch, f, sred, band_rows, chmask, spitch, sframe);
     } else {
         b -= n_alt;
         const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);
-        fc_edge_strips_body<CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f);
+        fc_edge_strips_body<CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f, spitch, sframe);
     }
 }
 

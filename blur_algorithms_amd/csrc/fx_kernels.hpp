@@ -806,8 +806,9 @@ inline int fx_right_strips(int cols, int pada)
 // v_perm_b32), or -- image widths that are not multiples of 4, tiny images -- straddles an edge and is gathered pixel by pixel.
 // work items (fx_prepass): blocks over ceil(rows / 4) x win / 4 threads (4 rows of one group each) x strips x frames
 // narrow (fx_blur_u8's strips): only the groups of fx_strip_range are written (the kernel reads the others from the image)
+// spitch, sframe: the source's row pitch and frame stride in bytes (3 cols and 3 rows cols for a packed frame; the strips are packed)
 __device__ __forceinline__ void fx_edge_strips_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ strips, int rows, int cols, int pada, int chunks, int nright,
-                                                    int bx, int sidx, int f, int narrow)
+                                                    int bx, int sidx, int f, int narrow, uint32_t spitch, size_t sframe)
 {
     const int win = kFxChunk + 2 * pada, gpr = win / 4;
     const int nleft = fx_left_strips(pada);
@@ -827,12 +828,12 @@ __device__ __forceinline__ void fx_edge_strips_body(const uint8_t* __restrict__ 
     const int xs = X < 0 ? -X - 3 : (X >= cols ? 2 * cols - 5 - X : X);
     const bool fast = xs >= 0 && xs + 3 < cols;
     typedef uint32_t u3 __attribute__((ext_vector_type(3)));
-    const uint8_t* img = src + static_cast<size_t>(f) * rows * cols * 3;
+    const uint8_t* img = src + static_cast<size_t>(f) * sframe;
     uint8_t* sbase = strips + (static_cast<size_t>(f) * (nleft + nright) + sidx) * rows * (3 * win) + 12 * gidx;
     u3 d[4];
     if (fast) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) d[k] = *reinterpret_cast<const u3*>(img + (static_cast<size_t>(min(4 * r4 + k, rows - 1)) * cols + xs) * 3);
+        for (int k = 0; k < 4; ++k) d[k] = *reinterpret_cast<const u3*>(img + static_cast<size_t>(min(4 * r4 + k, rows - 1)) * spitch + 3 * xs);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -847,7 +848,7 @@ __device__ __forceinline__ void fx_edge_strips_body(const uint8_t* __restrict__ 
                 o[2] = __builtin_amdgcn_perm(d[k][1], d[k][0], 0x02010005u);
             }
         } else {             // reaches past one reflection (tiny images): pixel by pixel
-            const uint8_t* line = img + static_cast<size_t>(r) * cols * 3;
+            const uint8_t* line = img + static_cast<size_t>(r) * spitch;
             uint32_t b[12];
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
@@ -899,14 +900,16 @@ inline int fx_band_rows(int rows, int cols, int nframes, int num_cus)
 // compiler would turn into a serial loop over the lanes, and a DPP reduction costs twelve dependent instructions)
 // G = groups per thread and row (1, 2, 4): a batch is 256 G groups wide, so that an image of up to 4096 G pixel columns has at most
 // kFxMaxBatches batches (the fused kernel adds a row's batch parts up with that many unconditional loads)
+// spitch, sframe: the source's row pitch and frame stride in bytes; no load leaves its row's 3 cols bytes, the sums stay packed
 template <int G>
 __device__ __forceinline__ void fx_altsums_body(const uint8_t* __restrict__ src, int* __restrict__ srow_part, int* __restrict__ cpart, long long* __restrict__ zpart,
-                                                int rows, int cols, int pad, int nbands, int nbatches, int band, int batch, int f, int (*sred)[3][64], int band_rows)
+                                                int rows, int cols, int pad, int nbands, int nbatches, int band, int batch, int f, int (*sred)[3][64], int band_rows,
+                                                uint32_t spitch, size_t sframe)
 {
     const int tid = threadIdx.x;
-    const uint8_t* img = src + static_cast<size_t>(f) * rows * cols * 3;
+    const uint8_t* img = src + static_cast<size_t>(f) * sframe;
     // (a buffer resource per frame: 32-bit offsets, and nothing outside the frame can be touched)
-    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(img), 0, static_cast<uint32_t>(rows) * cols * 3u, kMxRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(img), 0, static_cast<uint32_t>(rows - 1) * spitch + static_cast<uint32_t>(cols) * 3u, kMxRsrcWord3);
     const int groups = (cols + 3) / 4, r0 = band * band_rows, r1 = min(r0 + band_rows, rows);
     const int flip = (pad & 1) ? -1 : 1;
     // a width that is no multiple of 4 (cols >= 4): the LAST group of a row is loaded from pixel cols - 4, overlapping the group before
@@ -952,7 +955,7 @@ __device__ __forceinline__ void fx_altsums_body(const uint8_t* __restrict__ src,
             for (int i = 0; i < RB; ++i) {
                 const int r = min(rb + i, re - 1);
 #pragma unroll
-                for (int j = 0; j < G; ++j) d[i][j] = __builtin_amdgcn_raw_buffer_load_b96(rimg, col0[j] + static_cast<uint32_t>(r) * static_cast<uint32_t>(cols) * 3u, 0, 0);
+                for (int j = 0; j < G; ++j) d[i][j] = __builtin_amdgcn_raw_buffer_load_b96(rimg, col0[j] + static_cast<uint32_t>(r) * spitch, 0, 0);
             }
 #pragma unroll
             for (int i = 0; i < RB; ++i) {
@@ -1053,17 +1056,17 @@ __device__ __forceinline__ void fx_altsums_body(const uint8_t* __restrict__ src,
 template <int G>
 __global__ __launch_bounds__(256) void fx_prepass(const uint8_t* __restrict__ src, int* __restrict__ srow_part, int* __restrict__ cpart, long long* __restrict__ zpart,
                                                   uint8_t* __restrict__ strips, int rows, int cols, int pad, int pada, int nbands, int nbatches, int n_alt, int chunks,
-                                                  int nright, int strip_blocks, int band_rows, int narrow)
+                                                  int nright, int strip_blocks, int band_rows, int narrow, uint32_t spitch, size_t sframe)
 {
     __shared__ int sred[kFxSumRows][3][64];
     int b = blockIdx.x;
     if (b < n_alt) {
         const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
-        fx_altsums_body<G>(src, srow_part, cpart, zpart, rows, cols, pad, nbands, nbatches, band, batch, f, sred, band_rows);
+        fx_altsums_body<G>(src, srow_part, cpart, zpart, rows, cols, pad, nbands, nbatches, band, batch, f, sred, band_rows, spitch, sframe);
     } else {
         b -= n_alt;
         const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);
-        fx_edge_strips_body(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f, narrow);
+        fx_edge_strips_body(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f, narrow, spitch, sframe);
     }
 }
 #endif  // BLUR_FX_QUIRK_KERNELS

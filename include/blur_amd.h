@@ -483,6 +483,58 @@ int blur_gaussian_bf16_sigmas_batch_multi_dev(blur_multi* m, const uint16_t* d_s
                                               const double* sigmas, const blur_opts* opts);
 int blur_gaussian_bf16_sigmas_batch_multi_host(blur_multi* m, const uint16_t* src, uint16_t* dst, int nframes, int rows, int cols, int channels,
                                                const double* sigmas, const blur_opts* opts);
+/* ---- pitched frames and regions of interest, DEVICE pointers ---------------------------------------------------------------
+   The entries above take densely packed frames.  These take frames whose rows lie src_pitch / dst_pitch BYTES apart and whose
+   frames lie src_frame_stride / dst_frame_stride BYTES apart, for the source and the destination independently: a
+   hipMallocPitch or decoder surface (1920 pixels in a 2048-pixel pitch), or a region of interest inside a larger image (a
+   cv::Mat ROI: data pointer of the ROI's first pixel, pitch = Mat::step; the frames of a batch of such views lie one parent frame
+   apart).  Nothing is repacked: the kernels address the rows through the pitches, and no byte of the destination outside the
+   rows x cols rectangles is written (every store is masked by x < cols).  The result in the rectangle is, bit for bit, what the
+   packed entry of the same type returns for the packed copy of the source -- with one exception: three-channel u8 frames with
+   one sigma run on the one-channel-per-workgroup kernel here (the route of the _sigmas_ entries) where the packed entry has its
+   three-channel kernel; both meet the u8 parity contract, a rounding tie may fall differently.
+   Overlap: the byte spans [base, base + (nframes - 1) frame_stride + (rows - 1) pitch + cols channels sizeof(element)) of the
+   source and the destination are compared.  Where they intersect -- an in-place call, two rectangles of one parent image -- the
+   source rectangles are first gathered into the context's workspace (one launch on the call's stream), so the result is always
+   what reading the whole source before the first write gives.
+   Arguments: the rules of the packed entry of the type (sigma, sizes, engine), and BLUR_ERR_INVALID for a pitch below
+   cols * channels * sizeof(element), a pitch or frame stride that is no multiple of sizeof(element), and, with nframes > 1, a
+   frame stride below (rows - 1) * pitch + cols * channels * sizeof(element); checked before the device is touched (ctx may then
+   be NULL).  A frame stride of 0 with nframes == 1 is accepted.  A frame whose span (rows - 1) * pitch + cols * channels *
+   sizeof(element) exceeds 4 GiB - 4 KiB takes the plane path, or fails with BLUR_ERR_UNSUPPORTED under engine = FUSED, as a packed
+   frame of that size does.  pitch = cols * channels * sizeof(element) and frame_stride = rows * pitch is the packed entry. */
+int blur_gaussian_u8_pitched_batch_dev(blur_ctx* ctx, const uint8_t* d_src, size_t src_pitch, size_t src_frame_stride, uint8_t* d_dst,
+                                       size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                       double sigma, const blur_opts* opts);
+int blur_gaussian_f32_pitched_batch_dev(blur_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst,
+                                        size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                        double sigma, const blur_opts* opts);
+int blur_gaussian_u16_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                        size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                        double sigma, const blur_opts* opts);
+int blur_gaussian_f16_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                        size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                        double sigma, const blur_opts* opts);
+int blur_gaussian_bf16_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                         size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                         double sigma, const blur_opts* opts);
+/* one sigma per channel (the _sigmas_ entries' rules: 0 leaves the channel as it is; its samples in the rectangle are copied) */
+int blur_gaussian_u8_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint8_t* d_src, size_t src_pitch, size_t src_frame_stride, uint8_t* d_dst,
+                                              size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                              const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f32_sigmas_pitched_batch_dev(blur_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst,
+                                               size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                               const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                               size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                               const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                               size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                               const double* sigmas, const blur_opts* opts);
+int blur_gaussian_bf16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                                size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                                const double* sigmas, const blur_opts* opts);
+
 /* host-only plan of the calls above (no GPU needed; the same host code the entries use): for channel c, out[3 c] = its group (the
    channels of equal sigma share an index, counted in the order of their first channel; -1 for sigma = 0), out[3 c + 1] = the pad
    of its sigma on this frame, out[3 c + 2] = the fused kernel's window class NKB, 8 (NKB - 4) < pad <= 8 (NKB - 2), or 0 where the

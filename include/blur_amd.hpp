@@ -287,6 +287,71 @@ inline void gaussian_blur_bf16(uint16_t* bits, int rows, int cols, int channels,
     check(ctx, blur_gaussian_bf16_sigmas_host(ctx, bits, bits, rows, cols, channels, sigmas, opts), "gaussian_blur_bf16");
 }
 
+// DEVICE frames whose rows lie `step` bytes apart (cv::Mat::step of a region of interest, a hipMallocPitch surface): one frame,
+// source and destination each with its own step, nothing repacked and nothing outside the rows x cols rectangle written
+// (blur_gaussian_*_pitched_batch_dev; d_dst may be d_src, and two rectangles of one image may overlap in memory: the source is
+// then read whole first).  Asynchronous on the context's stream.  sigma: a double, or const double* sigmas[channels].
+inline void gaussian_blur_dev(const uint8_t* d_src, size_t src_step, uint8_t* d_dst, size_t dst_step, int rows, int cols, int channels, double sigma,
+                              blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u8_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigma, opts), "gaussian_blur_dev");
+}
+inline void gaussian_blur_dev(const float* d_src, size_t src_step, float* d_dst, size_t dst_step, int rows, int cols, int channels, double sigma,
+                              blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f32_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigma, opts), "gaussian_blur_dev");
+}
+inline void gaussian_blur_dev(const uint16_t* d_src, size_t src_step, uint16_t* d_dst, size_t dst_step, int rows, int cols, int channels, double sigma,
+                              blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u16_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigma, opts), "gaussian_blur_dev");
+}
+inline void gaussian_blur_f16_dev(const uint16_t* d_src, size_t src_step, uint16_t* d_dst, size_t dst_step, int rows, int cols, int channels, double sigma,
+                                  blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f16_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigma, opts), "gaussian_blur_f16_dev");
+}
+inline void gaussian_blur_bf16_dev(const uint16_t* d_src, size_t src_step, uint16_t* d_dst, size_t dst_step, int rows, int cols, int channels, double sigma,
+                                   blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_bf16_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigma, opts), "gaussian_blur_bf16_dev");
+}
+inline void gaussian_blur_dev(const uint8_t* d_src, size_t src_step, uint8_t* d_dst, size_t dst_step, int rows, int cols, int channels, const double* sigmas,
+                              blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u8_sigmas_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigmas, opts), "gaussian_blur_dev");
+}
+inline void gaussian_blur_dev(const float* d_src, size_t src_step, float* d_dst, size_t dst_step, int rows, int cols, int channels, const double* sigmas,
+                              blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f32_sigmas_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigmas, opts), "gaussian_blur_dev");
+}
+inline void gaussian_blur_dev(const uint16_t* d_src, size_t src_step, uint16_t* d_dst, size_t dst_step, int rows, int cols, int channels, const double* sigmas,
+                              blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u16_sigmas_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigmas, opts), "gaussian_blur_dev");
+}
+inline void gaussian_blur_f16_dev(const uint16_t* d_src, size_t src_step, uint16_t* d_dst, size_t dst_step, int rows, int cols, int channels, const double* sigmas,
+                                  blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f16_sigmas_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigmas, opts), "gaussian_blur_f16_dev");
+}
+inline void gaussian_blur_bf16_dev(const uint16_t* d_src, size_t src_step, uint16_t* d_dst, size_t dst_step, int rows, int cols, int channels, const double* sigmas,
+                                   blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_bf16_sigmas_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigmas, opts), "gaussian_blur_bf16_dev");
+}
+
 // pocketfft_1D(image, sigma) (Source.cpp:280-392) and pocketfft_2D(image, sigma) (Source.cpp:143-277): the two
 // pocketfft paths multiply all N/2+1 bins with the kernel's own spectrum (no Nyquist-slot quirk) and, inside the
 // cropped image, both equal the linear convolution of the reflect-101 extended image -- the engine's
