@@ -7,4 +7,4 @@ is the thin host-side mirror of the reference's call surface over it.
 from ._lib import BlurError, LIB_PATH  # noqa: F401
 from .api import (BlurContext, BlurMulti, gaussian_window, getGaussian, isValidSize, nearestTransformSize,  # noqa: F401
                   pffft_sizing, kernel_multipliers, fft_plan_radices, box_kernel, boxfft_sizing,
-                  fastboxblur_batch_plan, gaussian_sigmas_plan)
+                  fastboxblur_batch_plan, gaussian_sigmas_plan, gaussian_frame_sigmas_plan)

@@ -270,6 +270,28 @@ def gaussian_sigmas_plan(rows, cols, sigmas):
     return [(out[3 * c], out[3 * c + 1], out[3 * c + 2]) for c in range(len(vals))]
 
 
+def gaussian_frame_sigmas_plan(rows, cols, sigmas):
+    """how a one-sigma-per-frame Gaussian call groups its frames (host only, no GPU): a list with one (group, pad, nkb, slot) per
+    frame.  group: the frames of one window class share a launch and an index, counted by first frame, -1 for sigma = 0 (the frame
+    is copied); pad: pffft_sizing's; nkb: the fused kernel's window class, 0 where the pad has none (pad > 168: the plane path);
+    slot: frames of equal sigma share their tables and an index, -1 for sigma = 0"""
+    vals = [float(v) for v in sigmas]
+    out = (C.c_int * max(1, 4 * len(vals)))()
+    rc = _L().blur_gaussian_frame_sigmas_plan(int(rows), int(cols), len(vals), (C.c_double * max(1, len(vals)))(*vals), out)
+    if rc:
+        raise BlurError(rc, "gaussian_frame_sigmas_plan: bad arguments")
+    return [(out[4 * f], out[4 * f + 1], out[4 * f + 2], out[4 * f + 3]) for f in range(len(vals))]
+
+
+def _broadcast_frames_layout(t):
+    """(pitch, 0) in elements for frames [n, rows, cols, C] that all are one frame (`img.expand(n, -1, -1, -1)`: frame stride 0), None
+    for any other tensor"""
+    if t.dim() != 4 or t.shape[0] < 2 or t.stride(0) != 0:
+        return None
+    one = _gauss_strided_layout(tuple(t.shape[1:]), tuple(t.stride()[1:]))
+    return None if one is None else (one[0], 0)
+
+
 def fft_plan_radices(n):
     r = (C.c_int * 16)()
     k = _L().blur_fft_plan_radices(int(n), r)
@@ -659,6 +681,73 @@ class BlurContext:
         torch.bfloat16 tensor: host round trip, returns a new CPU tensor (numpy has no bfloat16; a numpy array is refused).
         """
         return self._gaussian(image, sigma, out, nyquist_quirk, engine, BF16, "bf16")
+
+    def gaussian_per_frame(self, frames, sigmas, out=None, nyquist_quirk=True, engine=None):
+        """Gaussian blur of uint8 frames [n, rows, cols, C] or [n, rows, cols] (C in {1, 3, 4}) with one sigma per FRAME: `sigmas` is a
+        sequence of n numbers, frame f is what gaussian() returns for it alone with sigmas[f], and 0 copies the frame
+        (blur_gaussian_u8_frame_sigmas_batch_dev: the frames of one window class share one launch, whatever their sigmas).  The
+        one exception to "what gaussian() returns": three-channel frames run on the one-channel-per-workgroup kernel, never on
+        gaussian()'s three-channel kernels, and meet the same oracle; with ONE sigma for all BGR frames call gaussian().
+        engine: None (the library's choice), "fused" or "fft", frame by frame.
+
+        torch CUDA tensor: asynchronous on torch's current stream, returns `out` (default: in place).  The tensor, and `out`
+        independently, may be the pitched views gaussian() accepts.  A source whose frame stride is 0 -- `img.expand(k, -1, -1,
+        -1)`: one frame, k sigmas, k results (scale space, difference of Gaussians) -- is accepted too and needs `out`.
+        numpy array: host round trip frame by frame through the scalar entry, returns a new array.
+        """
+        return self._gaussian_per_frame(frames, sigmas, out, nyquist_quirk, engine, np.uint8, "u8")
+
+    def gaussian_f32_per_frame(self, frames, sigmas, out=None, nyquist_quirk=True, engine=None):
+        """gaussian_per_frame for float32 frames: frame f is, bit for bit, what gaussian_f32() returns for it alone with sigmas[f] (its
+        power-of-two scale comes from its own max|x|), for 1, 3 and 4 channels (blur_gaussian_f32_frame_sigmas_batch_dev)."""
+        return self._gaussian_per_frame(frames, sigmas, out, nyquist_quirk, engine, np.float32, "f32")
+
+    def _gaussian_per_frame(self, frames, sigmas, out, nyquist_quirk, engine, dtype, tname):
+        o = self._opts(nyquist_quirk, engine=engine)
+        vals = [float(v) for v in sigmas]
+        if len(frames.shape) not in (3, 4):
+            raise ValueError("expected frames [n, rows, cols, C] or [n, rows, cols]")
+        if len(vals) != frames.shape[0]:
+            raise ValueError("sigmas: expected one per frame (%d), got %d" % (frames.shape[0], len(vals)))
+        sg = (C.c_double * max(1, len(vals)))(*vals)
+        if _is_host_frames(frames, dtype):
+            a, res, _ = _gauss_array(frames if frames.ndim == 4 else frames[..., None], out if out is None or out.ndim == 4 else out[..., None], dtype, batch=True)
+            n, rows, cols, ch = a.shape
+            host_entry = getattr(self._lib, "blur_gaussian_%s_host" % tname)
+            for f in range(n):
+                if vals[f] == 0:
+                    res[f] = a[f]
+                else:
+                    self._check(host_entry(self._h, a[f].ctypes.data, res[f].ctypes.data, rows, cols, ch, vals[f], C.byref(o)))
+            return res if frames.ndim == 4 or out is not None else res[..., 0]
+        import torch
+        t4 = frames.unsqueeze(-1) if isinstance(frames, torch.Tensor) and frames.dim() == 3 else frames
+        o4 = out.unsqueeze(-1) if isinstance(out, torch.Tensor) and out.dim() == 3 else out
+        bl = _broadcast_frames_layout(t4) if isinstance(t4, torch.Tensor) else None
+        if bl is not None:
+            if o4 is None:
+                raise ValueError("frames with a frame stride of 0 (one frame, several sigmas) need `out`: there is no in-place result")
+            # (the checks of _gauss_tensor on one frame of the source and on the whole result)
+            _gauss_tensor(t4[0], None, dtype)
+            _, dst, (n, rows, cols, ch), _ = _gauss_tensor(o4, None, dtype)
+            if tuple(o4.shape) != tuple(t4.shape):
+                raise ValueError("out must match the input")
+            es = t4.element_size()
+            dl = _gauss_strided_layout(dst.shape, dst.stride())
+            lay = (bl[0] * es, 0, dl[0] * es, dl[1] * es)
+            t = t4
+        else:
+            t, dst, (n, rows, cols, ch), lay = _gauss_tensor(t4, o4, dtype)
+            if t.dim() != 4:
+                raise ValueError("expected frames [n, rows, cols, C] or [n, rows, cols]")
+        self.use_torch_stream()
+        if lay is not None:
+            pitched_entry = getattr(self._lib, "blur_gaussian_%s_frame_sigmas_pitched_batch_dev" % tname)
+            self._check(pitched_entry(self._h, t.data_ptr(), lay[0], lay[1], dst.data_ptr(), lay[2], lay[3], n, rows, cols, ch, sg, C.byref(o)))
+        else:
+            batch_entry = getattr(self._lib, "blur_gaussian_%s_frame_sigmas_batch_dev" % tname)
+            self._check(batch_entry(self._h, t.data_ptr(), dst.data_ptr(), n, rows, cols, ch, sg, C.byref(o)))
+        return frames if out is None else out
 
     def _gaussian(self, image, sigma, out, nyquist_quirk, engine, dtype, tname):
         """tname: the entry points' type name (blur_gaussian_<tname>_host, _batch_dev; a sequence `sigma`: _sigmas_host, _sigmas_batch_dev)"""

@@ -773,6 +773,14 @@ struct blur_ctx {
     size_t ff_sums_bytes = 0;
     void* ff_strips = nullptr;       // float32 / u16 / half images, fused kernel: the edge chunks' windows (samples of the frame's type)
     size_t ff_strips_bytes = 0;
+    // one sigma per frame (blur_ch_frame_sigmas_batch_impl): the call's frame list, fragments and taps on the device, and the pinned
+    // host memory they are uploaded from; fs_uploaded is recorded behind the upload that last read the staging memory
+    void* fs_table = nullptr;
+    size_t fs_table_bytes = 0;
+    void* fs_stage = nullptr;
+    size_t fs_stage_bytes = 0;
+    hipEvent_t fs_uploaded = nullptr;
+    bool fs_pending = false;
     size_t box_bytes = 0;
     std::string engine_note;      // BLUR_ENGINE_AUTO: why the last call's choice passed over a faster engine ("" if it did not)
     int last_family = -1;         // kernels the last u8c3 blur used: 0 run-time plans, 1 specialised rows-first, 2 wave-resident, 3 whole-image 2D, 4 matrix-core (two kernels), 6 fused matrix-core
@@ -1137,91 +1145,116 @@ static uint64_t fnv1a(const void* data, size_t bytes)
 }
 
 // ---- matrix-core engine: tables ----------------------------------------------------------------------------------
-// taps of one axis from the reference's n-periodic kernel array (centre at index 0): taps[t + pad] = karr[(t + n) % n]
-// quiet: a kernel the engine cannot hold is reported by the return value only (the caller falls back to another engine)
-static int mx_get_tables(blur_ctx* ctx, int nkb, double sigma, const Sizing& sz, const CustomKernel* ck, const MxTables** out, bool quiet = false)
+// What the matrix-core kernels read for one kernel, as the host makes it from (sigma | a caller's kernel, Sizing, nkb) alone:
+// mx_get_tables uploads and caches it per context; the one-sigma-per-frame entries (blur_ch_frame_sigmas_batch_impl) put the tables
+// of a whole call into one upload instead, from this same code: what a frame is blurred with cannot differ between the two.
+struct MxHostTables {
+    std::vector<uint16_t> frags[2];   // row axis, column axis: [2][nkb][64][8] binary16 (host_math.hpp: mx_fragments)
+    std::vector<float> taps_row;      // 2 pad + 1 floats, centre at pad (the same taps serve both axes)
+    float dr = 0.f, dc = 0.f;         // m[0] - m[N/2] of the reference's row / column transform length (the quirk's gain)
+};
+
+// the reference's n-periodic kernel arrays (centre at index 0) of the row axis (n_row) and the column axis (n_col)
+static int mx_kernel_arrays(double sigma, const Sizing& sz, const CustomKernel* ck, std::vector<float> (&karr)[2], const char** why)
 {
-    auto refuse = [&](int code, const char* msg) { return quiet ? code : fail(ctx, code, msg); };
-    const int pad = sz.pad;
-    std::vector<float> karr[2];                                  // row axis (n_row), column axis (n_col)
     const int nn[2] = { sz.n_row, sz.n_col };
-    uint64_t tag;
-    int kkey;
-    auto build_arrays = [&]() -> int {
-        for (int ax = 0; ax < 2; ++ax) {
-            const int n = nn[ax];
-            if (ck) {
-                karr[ax].assign(n, 0.f);
-                if (ck->box_klen > 0) box_kernel_1d(karr[ax].data(), ck->box_klen, n);
-                else {
-                    if (ck->ksize > n) return refuse(BLUR_ERR_INVALID, "kernel longer than the padded line");
-                    const int c = ck->ksize / 2;
-                    for (int t = 0; t < ck->ksize; ++t) karr[ax][(t - c + n) % n] += ck->taps[t];
-                }
-            } else {
-                karr[ax].assign(std::max(n, sz.kSize), 0.f);
-                get_gaussian(karr[ax].data(), sigma, sz.kSize, n);    // Source.cpp:75-102
+    for (int ax = 0; ax < 2; ++ax) {
+        const int n = nn[ax];
+        if (ck) {
+            karr[ax].assign(n, 0.f);
+            if (ck->box_klen > 0) box_kernel_1d(karr[ax].data(), ck->box_klen, n);
+            else {
+                if (ck->ksize > n) { *why = "kernel longer than the padded line"; return BLUR_ERR_INVALID; }
+                const int c = ck->ksize / 2;
+                for (int t = 0; t < ck->ksize; ++t) karr[ax][(t - c + n) % n] += ck->taps[t];
             }
+        } else {
+            karr[ax].assign(std::max(n, sz.kSize), 0.f);
+            get_gaussian(karr[ax].data(), sigma, sz.kSize, n);    // Source.cpp:75-102
         }
-        return BLUR_OK;
-    };
-    // the Gaussian's key needs no kernel array: look it up before building one
-    if (ck) {
-        if (int rc = build_arrays()) return rc;
-        kkey = -1;
-        tag = fnv1a(karr[0].data(), nn[0] * sizeof(float)) ^ (fnv1a(karr[1].data(), nn[1] * sizeof(float)) * 3);
-    } else { kkey = sz.kSize; std::memcpy(&tag, &sigma, sizeof tag); }
-    // (pad and nkb are part of the key: the same taps with another pad, or the two-kernel and the fused engine with different
-    // window sizes for one pad, have different fragment tables)
-    const auto key = std::make_tuple(kkey, pad, nkb, nn[0], nn[1], tag);
-    auto it = ctx->mx_tables.find(key);
-    if (it != ctx->mx_tables.end()) { *out = &it->second; return BLUR_OK; }
-    if (!ck) { if (int rc = build_arrays()) return rc; }
-    MxTables t;
-    auto release = [&]() {                                        // a failure on the second axis must not leak the first one's tables
-        if (t.frags_row) (void)hipFree(t.frags_row);
-        if (t.frags_col) (void)hipFree(t.frags_col);
-        if (t.taps_row) (void)hipFree(t.taps_row);
-    };
+    }
+    return BLUR_OK;
+}
+
+// taps of one axis from the kernel array: taps[t + pad] = karr[(t + n) % n]; fragments, taps and gains of both axes.  Host only.
+// col_frags = false: the column axis is checked and its gain made, its fragments are not (the fused kernels read the row axis')
+static int mx_host_tables(const std::vector<float> (&karr)[2], const Sizing& sz, int nkb, MxHostTables& t, const char** why, bool col_frags = true)
+{
+    const int pad = sz.pad;
+    const int nn[2] = { sz.n_row, sz.n_col };
     for (int ax = 0; ax < 2; ++ax) {
         const int n = nn[ax];
         std::vector<float> taps(2 * pad + 1);
         for (int k = -pad; k <= pad; ++k) taps[k + pad] = karr[ax][(k + n) % n];
         // anything of the kernel array outside +-pad would be lost here: the Toeplitz band is 2 pad + 1 wide
         for (int i = pad + 1; i < n - pad; ++i)
-            if (karr[ax][i] != 0.f) { release(); return refuse(BLUR_ERR_UNSUPPORTED, "matrix-core engine: kernel wider than 2 pad + 1"); }
+            if (karr[ax][i] != 0.f) { *why = "matrix-core engine: kernel wider than 2 pad + 1"; return BLUR_ERR_UNSUPPORTED; }
         // the 24-bit intermediate of the two-kernel engine (mx_kernels.hpp) covers [0, 256): non-negative taps with sum <= 1 keep the
         // row pass inside 0..255.13 (the quirk's terms are added in f32 after it is decoded: no bound on them)
         {
             double sum = 0;
             bool neg = false;
-            for (float t : taps) { sum += t; neg = neg || t < 0.f; }
-            if (neg || sum > 1.0005) { release(); return refuse(BLUR_ERR_UNSUPPORTED, "matrix-core engine: taps must be non-negative with sum <= 1"); }
+            for (float v : taps) { sum += v; neg = neg || v < 0.f; }
+            if (neg || sum > 1.0005) { *why = "matrix-core engine: taps must be non-negative with sum <= 1"; return BLUR_ERR_UNSUPPORTED; }
         }
-        std::vector<uint16_t> fr(static_cast<size_t>(2) * nkb * 512);
-        mx_fragments(taps.data(), pad, nkb, fr.data());
+        if (ax == 0 || col_frags) {
+            t.frags[ax].resize(static_cast<size_t>(2) * nkb * 512);
+            mx_fragments(taps.data(), pad, nkb, t.frags[ax].data());
+        }
         // m[0] and m[n/2] as host_math's kernel_multipliers computes them: float(Re DFT) * (1.f / n)
         long double k0 = 0, kalt = 0;
         for (int i = 0; i < n; ++i) { k0 += karr[ax][i]; kalt += (i & 1) ? -static_cast<long double>(karr[ax][i]) : static_cast<long double>(karr[ax][i]); }
         const float scaler = 1.f / n;
         const float m0 = static_cast<float>(k0) * scaler, mh = static_cast<float>(kalt) * scaler;
-        void* dfr = nullptr;
-        hipError_t e = hipMalloc(&dfr, fr.size() * sizeof(uint16_t));
-        if (e == hipSuccess) {
-            (ax ? t.frags_col : t.frags_row) = dfr;
-            e = hipMemcpy(dfr, fr.data(), fr.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess && ax == 0) {                        // the taps themselves: the fused engine's quirk terms convolve with them
-            e = hipMalloc(reinterpret_cast<void**>(&t.taps_row), taps.size() * sizeof(float));
-            if (e == hipSuccess) e = hipMemcpy(t.taps_row, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice);
-        }
-        if (e != hipSuccess) {
-            release();
-            (void)hipGetLastError();          // clear it: under AUTO the caller falls back to another engine, whose first launch check would pick it up
-            if (!quiet) ctx->err = std::string("matrix-core tables: ") + hipGetErrorString(e);
-            return BLUR_ERR_HIP;
-        }
         (ax ? t.dc : t.dr) = m0 - mh;
+        if (ax == 0) t.taps_row = std::move(taps);               // the taps themselves: the fused engine's quirk terms convolve with them
+    }
+    return BLUR_OK;
+}
+
+// The tables of one kernel on the device, cached in the context (the scalar entries: a few sigmas per context).
+// quiet: a kernel the engine cannot hold is reported by the return value only (the caller falls back to another engine)
+static int mx_get_tables(blur_ctx* ctx, int nkb, double sigma, const Sizing& sz, const CustomKernel* ck, const MxTables** out, bool quiet = false)
+{
+    auto refuse = [&](int code, const char* msg) { return quiet ? code : fail(ctx, code, msg); };
+    std::vector<float> karr[2];                                  // row axis (n_row), column axis (n_col)
+    const int nn[2] = { sz.n_row, sz.n_col };
+    const char* why = nullptr;
+    uint64_t tag;
+    int kkey;
+    // the Gaussian's key needs no kernel array: look it up before building one
+    if (ck) {
+        if (int rc = mx_kernel_arrays(sigma, sz, ck, karr, &why)) return refuse(rc, why);
+        kkey = -1;
+        tag = fnv1a(karr[0].data(), nn[0] * sizeof(float)) ^ (fnv1a(karr[1].data(), nn[1] * sizeof(float)) * 3);
+    } else { kkey = sz.kSize; std::memcpy(&tag, &sigma, sizeof tag); }
+    // (pad and nkb are part of the key: the same taps with another pad, or the two-kernel and the fused engine with different
+    // window sizes for one pad, have different fragment tables)
+    const auto key = std::make_tuple(kkey, sz.pad, nkb, nn[0], nn[1], tag);
+    auto it = ctx->mx_tables.find(key);
+    if (it != ctx->mx_tables.end()) { *out = &it->second; return BLUR_OK; }
+    if (!ck) { if (int rc = mx_kernel_arrays(sigma, sz, ck, karr, &why)) return refuse(rc, why); }
+    MxHostTables h;
+    if (int rc = mx_host_tables(karr, sz, nkb, h, &why)) return refuse(rc, why);
+    MxTables t;
+    t.dr = h.dr;
+    t.dc = h.dc;
+    auto upload = [](void** d, const void* src, size_t bytes) {
+        hipError_t e = hipMalloc(d, bytes);
+        if (e == hipSuccess) e = hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    hipError_t e = upload(&t.frags_row, h.frags[0].data(), h.frags[0].size() * sizeof(uint16_t));
+    if (e == hipSuccess) e = upload(reinterpret_cast<void**>(&t.taps_row), h.taps_row.data(), h.taps_row.size() * sizeof(float));
+    if (e == hipSuccess) e = upload(&t.frags_col, h.frags[1].data(), h.frags[1].size() * sizeof(uint16_t));
+    if (e != hipSuccess) {
+        // a failure on a later table must not leak the earlier ones
+        if (t.frags_row) (void)hipFree(t.frags_row);
+        if (t.frags_col) (void)hipFree(t.frags_col);
+        if (t.taps_row) (void)hipFree(t.taps_row);
+        (void)hipGetLastError();          // clear it: under AUTO the caller falls back to another engine, whose first launch check would pick it up
+        if (!quiet) ctx->err = std::string("matrix-core tables: ") + hipGetErrorString(e);
+        return BLUR_ERR_HIP;
     }
     *out = &(ctx->mx_tables[key] = t);
     return BLUR_OK;
@@ -1425,6 +1458,17 @@ static int plan_tiled(blur_ctx* ctx, int rows, int cols, double sigma, bool quir
     return BLUR_OK;
 }
 
+// the frames the fused kernels cannot take whatever the pad (null: none of these); prepare() and the one-sigma-per-frame entries
+static const char* fx_frame_limits(int rows, int cols, bool quirk)
+{
+    // (0xfffffff0 is the offset the kernels give a dropped store: it must lie outside the frame's buffer resource)
+    // (and the left chunk's image resource starts 3 pad bytes before the frame: its size is the frame's plus those)
+    if (static_cast<long long>(rows) * cols * 3 > 0xfffff000ll) return "fused matrix-core engine: frame too large for 32-bit offsets";
+    if (quirk && fx_groups_per_thread(cols) == 0) return "fused matrix-core engine: image wider than 16384 pixels (the quirk's pre-pass)";
+    if (quirk && cols < 4) return "fused matrix-core engine: image narrower than 4 pixels (the quirk's pre-pass)";
+    return nullptr;
+}
+
 static int prepare(blur_ctx* ctx, int rows, int cols, double sigma, const blur_opts* opts, Prepared& p, bool u8c3 = true,
                    const CustomKernel* ck = nullptr, bool allow_wr = true, bool ptrs_aligned = false)
 {
@@ -1497,11 +1541,7 @@ static int prepare(blur_ctx* ctx, int rows, int cols, double sigma, const blur_o
             else if (small_fft && fe->nkb >= 23) { fe = nullptr; why = "wide fused kernel: pad > 152 where the FFT engine has a compile-time family for the frame"; }
         }
         if (!fe && !why) why = "fused matrix-core engine: no kernel instantiated for this pad";
-        // (0xfffffff0 is the offset the kernels give a dropped store: it must lie outside the frame's buffer resource)
-        // (and the left chunk's image resource starts 3 pad bytes before the frame: its size is the frame's plus those)
-        else if (static_cast<long long>(rows) * cols * 3 > 0xfffff000ll) why = "fused matrix-core engine: frame too large for 32-bit offsets";
-        else if (quirk && fx_groups_per_thread(cols) == 0) why = "fused matrix-core engine: image wider than 16384 pixels (the quirk's pre-pass)";
-        else if (quirk && cols < 4) why = "fused matrix-core engine: image narrower than 4 pixels (the quirk's pre-pass)";
+        else if (const char* limit = fx_frame_limits(rows, cols, quirk)) why = limit;
         if (why && choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, why);
         if (why) ctx->engine_note = why;
         if (!why) {
@@ -1756,13 +1796,16 @@ static FwPitch fw_pitch_of(const ChLayout& L)
 }
 
 static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump, FwChSel chsel,
-                       const ChLayout* lay);
+                       const ChLayout* lay, const FwFrame* ft = nullptr);
 
 // the fused kernel for CH = 1, 4 (fw_kernels.hpp): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
 // Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).
 // chsel: the channels to blur (blur_ch_sigmas_batch_impl: one sigma per channel); the pre-pass reads every channel (a pixel is one
 // dword) and completes the quirk's row sums of these channels only
-static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel, const ChLayout& L)
+// ft: the frame list of a launch over frames with their own sigmas (blur_ch_frame_sigmas_batch_impl; FwFrame): nframes entries, whose
+// pads, fragments, taps and gains replace p's in the kernels
+static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel, const ChLayout& L,
+                     const FwFrame* ft = nullptr)
 {
     const FwPitch pt = fw_pitch_of(L);
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
@@ -1805,12 +1848,18 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
         long long* zsum = const_cast<long long*>(qk.zsum);
         auto kern = ch == 1 ? (G == 1 ? fc_prepass<1, 1> : (G == 2 ? fc_prepass<1, 2> : fc_prepass<1, 4>))
                             : (G == 1 ? fc_prepass<4, 1> : (G == 2 ? fc_prepass<4, 2> : fc_prepass<4, 4>));
-        hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, p.sz.pad, pada, nbands,
-                           nbatches, cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel), pt.src_pitch, pt.src_frame);
+        auto kern_frames = ch == 1 ? (G == 1 ? fc_prepass_frames<1, 1> : (G == 2 ? fc_prepass_frames<1, 2> : fc_prepass_frames<1, 4>))
+                                   : (G == 1 ? fc_prepass_frames<4, 1> : (G == 2 ? fc_prepass_frames<4, 2> : fc_prepass_frames<4, 4>));
+        if (ft)
+            hipLaunchKernelGGL(kern_frames, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, pada, nbands, nbatches,
+                               cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel), pt.src_pitch, pt.src_frame, ft);
+        else
+            hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, p.sz.pad, pada, nbands,
+                               nbatches, cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel), pt.src_pitch, pt.src_frame);
         HIP_TRY(ctx, hipGetLastError());
     }
     TimedLaunch t(ctx, 0, nframes);
-    HIP_TRY(ctx, fe->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel, pt));
+    HIP_TRY(ctx, fe->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel, pt, ft));
     return BLUR_OK;
 }
 
@@ -1819,8 +1868,10 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
 // partition of a sum (bands, batches) depends on the frame's shape only: a frame gives the same bits alone and in a batch.
 // T = float, uint16_t, ff_f16 or ff_bf16.  u16: no max|x| (the scale is a constant of the call), and without the quirk no sums at
 // all; the half types: as float.  chsel: the channels to blur (the pre-pass covers every channel either way: max|x| is the frame's).
+// ft: the frame list of a launch over frames with their own sigmas (run_fc_u8)
 template <typename T>
-static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel, const ChLayout& L)
+static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int ch, const Prepared& p, FwChSel chsel, const ChLayout& L,
+                  const FwFrame* ft = nullptr)
 {
     const FwPitch pt = fw_pitch_of(L);
     constexpr bool u16 = std::is_same_v<T, uint16_t>;
@@ -1872,18 +1923,26 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
         auto kern = ch == 1 ? pick(ff_prepass<T, 1, 1>, ff_prepass<T, 1, 2>, ff_prepass<T, 1, 4>)
                             : (ch == 3 ? pick(ff_prepass<T, 3, 1>, ff_prepass<T, 3, 2>, ff_prepass<T, 3, 4>)
                                        : pick(ff_prepass<T, 4, 1>, ff_prepass<T, 4, 2>, ff_prepass<T, 4, 4>));
-        if (n_alt + n_strip > 0)
+        auto kern_frames = ch == 1 ? pick(ff_prepass_frames<T, 1, 1>, ff_prepass_frames<T, 1, 2>, ff_prepass_frames<T, 1, 4>)
+                                   : (ch == 3 ? pick(ff_prepass_frames<T, 3, 1>, ff_prepass_frames<T, 3, 2>, ff_prepass_frames<T, 3, 4>)
+                                              : pick(ff_prepass_frames<T, 4, 1>, ff_prepass_frames<T, 4, 2>, ff_prepass_frames<T, 4, 4>));
+        if (n_alt + n_strip > 0 && ft)
+            hipLaunchKernelGGL(kern_frames, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, mbits, spart, cpart, strips, rows, cols, pada, nbands, nbatches, ne,
+                               n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0, pt.src_pitch, pt.src_frame, ft);
+        else if (n_alt + n_strip > 0)
             hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, mbits, spart, cpart, strips, rows, cols, p.sz.pad, pada, nbands,
                                nbatches, ne, n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0, pt.src_pitch, pt.src_frame);
         HIP_TRY(ctx, hipGetLastError());
         if (quirk) {
             auto fin = ch == 1 ? ff_finalize<1> : (ch == 3 ? ff_finalize<3> : ff_finalize<4>);
-            hipLaunchKernelGGL(fin, dim3(nframes), dim3(256), 0, ctx->stream, spart, srow, zsum, rows, p.sz.pad, nbatches);
+            auto fin_frames = ch == 1 ? ff_finalize_frames<1> : (ch == 3 ? ff_finalize_frames<3> : ff_finalize_frames<4>);
+            if (ft) hipLaunchKernelGGL(fin_frames, dim3(nframes), dim3(256), 0, ctx->stream, spart, srow, zsum, rows, nbatches, ft);
+            else hipLaunchKernelGGL(fin, dim3(nframes), dim3(256), 0, ctx->stream, spart, srow, zsum, rows, p.sz.pad, nbatches);
             HIP_TRY(ctx, hipGetLastError());
         }
     }
     TimedLaunch t(ctx, 0, nframes);
-    HIP_TRY(ctx, fe->blur(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, strips, chsel, pt));
+    HIP_TRY(ctx, fe->blur(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ch, ctx->num_cus, qk, quirk, strips, chsel, pt, ft));
     return BLUR_OK;
 }
 
@@ -2025,14 +2084,16 @@ static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nf
 }
 
 // the arguments a pitched entry adds (blur_gaussian_*_pitched_batch_dev), without the device: pitches and frame strides in bytes
-static int check_ch_layout(blur_ctx* ctx, int nframes, int rows, int cols, int channels, size_t es, const ChLayout& L)
+// src_broadcast: a source frame stride of 0 is accepted for any nframes (the one-sigma-per-frame entries: every frame of the result
+// is blurred from the same source frame)
+static int check_ch_layout(blur_ctx* ctx, int nframes, int rows, int cols, int channels, size_t es, const ChLayout& L, bool src_broadcast = false)
 {
     if (rows <= 0 || cols <= 0 || (channels != 1 && channels != 3 && channels != 4)) return BLUR_OK;       // (refused by the other checks)
     const size_t rowbytes = static_cast<size_t>(cols) * channels * es;
     if (L.spitch < rowbytes || L.dpitch < rowbytes) return fail(ctx, BLUR_ERR_INVALID, "row pitch below cols * channels * sizeof(element)");
     if (L.spitch % es || L.dpitch % es || L.sframe % es || L.dframe % es)
         return fail(ctx, BLUR_ERR_INVALID, "row pitch and frame stride must be multiples of the element size");
-    if (nframes > 1 && (L.sframe < ch_frame_span(rows, L.spitch, rowbytes) || L.dframe < ch_frame_span(rows, L.dpitch, rowbytes)))
+    if (nframes > 1 && ((L.sframe < ch_frame_span(rows, L.spitch, rowbytes) && !(src_broadcast && L.sframe == 0)) || L.dframe < ch_frame_span(rows, L.dpitch, rowbytes)))
         return fail(ctx, BLUR_ERR_INVALID, "frame stride below (rows - 1) * pitch + cols * channels * sizeof(element): the frames of the batch would overlap");
     return BLUR_OK;
 }
@@ -2418,6 +2479,260 @@ static int blur_ch_sigmas_host(blur_ctx* ctx, const T* src, T* dst, int rows, in
 }
 
 // ======================================================================================
+// One sigma per frame (blur_gaussian_{u8,f32}_frame_sigmas_*): frame f is what the scalar entry returns for it alone with
+// sigmas[f]; sigma = 0 copies the frame
+// ======================================================================================
+// The frames of a call by sigma and by window class.  slot: the distinct positive sigmas in the order of their first frame (frames
+// of equal sigma share their fragments and taps); group: the window classes in the order of their first frame (the frames of a
+// class share a fused launch; class 0 = the pads without a fused kernel)
+struct FrameSigmaPlan {
+    struct Slot { double sigma; Sizing sz; int nkb; int group; };
+    std::vector<Slot> slots;
+    std::vector<int> slot_of;            // per frame; -1: sigma = 0
+    std::vector<int> group_nkb;
+};
+
+// The arguments of every blur_gaussian_*_frame_sigmas_* entry, without a context or a device: the status and, where it is not
+// BLUR_OK, its text in *why.  Every entry of sigmas is checked here, before anything is launched: a refused call has written nothing.
+static int frame_sigmas_status(const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, FrameSigmaPlan& pl, const char** why)
+{
+    auto no = [&](int rc, const char* text) { *why = text; return rc; };
+    if (channels != 1 && channels != 3 && channels != 4) return no(BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
+    if (!src || !dst || nframes < 0) return no(BLUR_ERR_INVALID, "null frame pointer or negative frame count");
+    if (rows <= 0 || cols <= 0) return no(BLUR_ERR_INVALID, "rows and cols must be positive");
+    if (!sigmas) return no(BLUR_ERR_INVALID, "sigmas must point to one sigma per frame");
+    for (int f = 0; f < nframes; ++f)
+        if (!(sigmas[f] >= 0) || !std::isfinite(sigmas[f])) return no(BLUR_ERR_INVALID, "every sigma must be finite and positive, or 0 for a frame that is copied");
+    pl = FrameSigmaPlan{};
+    pl.slot_of.assign(nframes, -1);
+    std::map<double, int> seen;
+    std::map<int, int> group_of_nkb;
+    for (int f = 0; f < nframes; ++f) {
+        if (sigmas[f] == 0) continue;
+        auto it = seen.find(sigmas[f]);
+        if (it == seen.end()) {
+            FrameSigmaPlan::Slot sl{ sigmas[f], pffft_sizing(rows, cols, sigmas[f]), 0, 0 };
+            if (sl.sz.pad > rows - 1 || sl.sz.pad > cols - 1)
+                return no(BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1 for one of the sigmas: reflect-101 would read outside the image (README.md:33-38)");
+            const FxEntry* fe = find_fx_entry(sl.sz.pad);
+            sl.nkb = fe ? fe->nkb : 0;
+            auto g = group_of_nkb.find(sl.nkb);
+            if (g == group_of_nkb.end()) {
+                g = group_of_nkb.emplace(sl.nkb, static_cast<int>(pl.group_nkb.size())).first;
+                pl.group_nkb.push_back(sl.nkb);
+            }
+            sl.group = g->second;
+            it = seen.emplace(sigmas[f], static_cast<int>(pl.slots.size())).first;
+            pl.slots.push_back(sl);
+        }
+        pl.slot_of[f] = it->second;
+    }
+    return BLUR_OK;
+}
+
+// what a one-sigma-per-frame call reports of its frames on the plane path (blur_last_engine's note)
+struct FramePlaneNote {
+    int count = 0, first = -1;
+    double sigma = 0;
+    std::string why;
+};
+
+// The call's table -> the context's device workspace, in one upload on the call's stream.  The staging memory is pinned and
+// reused from call to call; the upload that last read it may still be in flight (the call is asynchronous), so its event is
+// waited for before the memory is rewritten -- the upload, not the kernels behind it.
+static int fs_upload(blur_ctx* ctx, const std::vector<unsigned char>& host)
+{
+    if (int rc = ensure_buf(ctx, &ctx->fs_table, &ctx->fs_table_bytes, host.size())) return rc;
+    if (ctx->fs_pending) {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->fs_uploaded));
+        ctx->fs_pending = false;
+    }
+    if (ctx->fs_stage_bytes < host.size()) {
+        if (ctx->fs_stage) { HIP_TRY(ctx, hipHostFree(ctx->fs_stage)); ctx->fs_stage = nullptr; ctx->fs_stage_bytes = 0; }
+        const size_t bytes = host.size() + host.size() / 2;
+        HIP_TRY(ctx, hipHostMalloc(&ctx->fs_stage, bytes, hipHostMallocDefault));
+        ctx->fs_stage_bytes = bytes;
+    }
+    if (!ctx->fs_uploaded) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fs_uploaded, hipEventDisableTiming));
+    std::memcpy(ctx->fs_stage, host.data(), host.size());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->fs_table, ctx->fs_stage, host.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->fs_uploaded, ctx->stream));
+    ctx->fs_pending = true;
+    return BLUR_OK;
+}
+
+// One driver over the element type, next to blur_ch_sigmas_batch_impl (u8 and float32 have entries; u16 and the half types would take
+// run_ff<T> as they do there).  Every distinct sigma gets the engine blur_ch_batch_impl's rules give it (the rules of choose_ch_engine;
+// u8 with three channels: those of one and four channels, on fw_blur_u8<NKB, Q, 3> -- never the u8c3 entry, whatever the sigmas: a
+// frame's bytes depend on its pixels, its sigma and opts alone) and its fragments, taps and gains from mx_host_tables, the code
+// behind the scalar entries' cached tables; nothing goes into ctx->mx_tables.  All of that happens before the first launch.  Then, on
+// the one stream: the copy of overlapping sources, the copies of the sigma = 0 frames (out of place only), the upload of the call's
+// table, and per window class the pre-pass and ONE fused launch over the class's frames (their list: FwFrame); the frames without
+// a fused kernel run one by one on the plane path.  The strips and sums workspaces are reused from class to class.
+// note: null for the call itself; the parts of a large in-place batch add to their caller's
+template <typename T>
+static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts,
+                                           const ChLayout* lay = nullptr, FramePlaneNote* note = nullptr, int frame0 = 0)
+{
+    constexpr bool u8 = std::is_same_v<T, uint8_t>, ffk = !u8;
+    FrameSigmaPlan pl;
+    if (lay)
+        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay, true)) return rc;
+    {
+        const char* why = nullptr;
+        if (int rc = frame_sigmas_status(d_src, d_dst, nframes, rows, cols, channels, sigmas, pl, &why)) return fail(ctx, rc, why);
+        if (!ctx) return BLUR_ERR_INVALID;
+    }
+    ChLayout L = lay ? *lay : ch_packed(rows, cols, channels, sizeof(T));
+    if (nframes == 1) L.sframe = L.dframe = 0;
+    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
+    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, (std::string(ch_type_name<T>()) + " images, one sigma per frame: engine must be AUTO, FUSED or FFT").c_str());
+    const bool quirk = opts ? opts->nyquist_quirk != 0 : true;
+    const size_t rowbytes = static_cast<size_t>(cols) * channels * sizeof(T), fb = rowbytes * rows;
+    // the engine and the tables of every distinct sigma
+    const int nslots = static_cast<int>(pl.slots.size());
+    std::vector<MxHostTables> tabs(nslots);
+    std::vector<const char*> why(nslots, nullptr);
+    std::vector<char> fused(nslots, 0);
+    for (int s = 0; s < nslots && choice != BLUR_ENGINE_FFT; ++s) {
+        const FrameSigmaPlan::Slot& sl = pl.slots[s];
+        const char* w = sl.nkb ? fx_frame_limits(rows, cols, quirk) : "fused matrix-core engine: no kernel instantiated for this pad";
+        if (!w) {
+            std::vector<float> karr[2];
+            if (mx_kernel_arrays(sl.sigma, sl.sz, nullptr, karr, &w) == BLUR_OK) (void)mx_host_tables(karr, sl.sz, sl.nkb, tabs[s], &w, false);
+        }
+        if (!w && ffk && !ff_class_ok_t<T>(sl.nkb, channels)) w = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
+        else if (!w && ffk && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(sl.nkb))
+            w = "fused kernel for float32 images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED";
+        else if (!w && std::max(ch_frame_span(rows, L.spitch, rowbytes), ch_frame_span(rows, L.dpitch, rowbytes)) > 0xfffff000ull)
+            w = "fused matrix-core engine: frame too large for 32-bit offsets";
+        if (w && choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, w);
+        why[s] = w;
+        fused[s] = w ? 0 : 1;
+    }
+    if (!note) ctx->engine_note.clear();
+    if (nframes == 0) return BLUR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool in_place = d_src == d_dst && L.spitch == L.dpitch && L.sframe == L.dframe;
+    if (in_place && nslots == 0) return BLUR_OK;                  // every frame is left as it is
+    FramePlaneNote mine;
+    FramePlaneNote& pn = note ? *note : mine;
+    if (ch_spans_overlap(d_src, d_dst, nframes, rows, rowbytes, L)) {
+        if (in_place) {             // in parts of at most 1 GiB (a part's result never touches a later part's source)
+            const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
+            if (static_cast<size_t>(nframes) > cap) {
+                for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
+                    const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
+                    T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * L.dframe);
+                    if (int rc = blur_ch_frame_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas + f0, opts, lay, &pn, frame0 + f0)) return rc;
+                }
+                nframes = 0;                                       // (the note is written below)
+            }
+        }
+        // one gathered copy of the source; a broadcast source (frame stride 0) is one frame
+        const bool broadcast = nframes > 1 && L.sframe == 0;
+        if (nframes > 0) {
+            if (int rc = ch_copy_source(ctx, &d_src, broadcast ? 1 : nframes, rows, rowbytes, L)) return rc;
+            if (broadcast || nframes == 1) L.sframe = 0;
+        }
+    }
+    auto src_of = [&](int f) { return reinterpret_cast<const T*>(reinterpret_cast<const char*>(d_src) + static_cast<size_t>(f) * L.sframe); };
+    auto dst_of = [&](int f) { return reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f) * L.dframe); };
+    // the sigma = 0 frames of an out-of-place call first
+    if (!in_place)
+        for (int f = 0; f < nframes; ++f)
+            if (pl.slot_of[f] < 0) HIP_TRY(ctx, hipMemcpy2DAsync(dst_of(f), L.dpitch, src_of(f), L.spitch, rowbytes, rows, hipMemcpyDeviceToDevice, ctx->stream));
+    // the call's table: [the frame lists of the classes, one behind the other][per fused sigma: its fragments, its taps]
+    std::vector<std::vector<int>> members(pl.group_nkb.size());
+    int nlisted = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const int s = pl.slot_of[f];
+        if (s >= 0 && fused[s]) { members[pl.slots[s].group].push_back(f); ++nlisted; }
+    }
+    if (nlisted > 0) {
+        auto up16 = [](size_t v) { return (v + 15) & ~static_cast<size_t>(15); };
+        size_t bytes = up16(static_cast<size_t>(nlisted) * sizeof(FwFrame));
+        std::vector<size_t> frags_at(nslots, 0), taps_at(nslots, 0);
+        std::vector<char> used(nslots, 0);
+        for (int f = 0; f < nframes; ++f)
+            if (pl.slot_of[f] >= 0 && fused[pl.slot_of[f]]) used[pl.slot_of[f]] = 1;
+        for (int s = 0; s < nslots; ++s) {
+            if (!used[s]) continue;
+            frags_at[s] = bytes;
+            bytes = up16(bytes + tabs[s].frags[0].size() * sizeof(uint16_t));
+            taps_at[s] = bytes;
+            bytes = up16(bytes + tabs[s].taps_row.size() * sizeof(float));
+        }
+        std::vector<unsigned char> host(bytes, 0);
+        FwFrame* list = reinterpret_cast<FwFrame*>(host.data());
+        int at = 0;
+        for (const std::vector<int>& m : members)
+            for (int f : m) {
+                const int s = pl.slot_of[f];
+                const MxHostTables& t = tabs[s];
+                const int pad = pl.slots[s].sz.pad;
+                // (bscale: B of ff_scale_exp, as run_ff makes it for a scalar call)
+                list[at++] = FwFrame{ f, pad, static_cast<uint32_t>(frags_at[s] / 16), static_cast<uint32_t>(taps_at[s] / sizeof(float)), t.dr, t.dc,
+                                      quirk ? 1.0 + std::fabs(static_cast<double>(t.dr)) * (static_cast<double>(cols) + 2.0 * pad) : 1.0 };
+            }
+        for (int s = 0; s < nslots; ++s) {
+            if (!used[s]) continue;
+            std::memcpy(host.data() + frags_at[s], tabs[s].frags[0].data(), tabs[s].frags[0].size() * sizeof(uint16_t));
+            std::memcpy(host.data() + taps_at[s], tabs[s].taps_row.data(), tabs[s].taps_row.size() * sizeof(float));
+        }
+        if (int rc = fs_upload(ctx, host)) return rc;
+        // per class: the pre-pass and one launch over its frames.  The runners take the class's kernel from p.fx, the table where a
+        // scalar call has its fragments and taps, and everything that depends on sigma from the list
+        MxTables table;
+        table.frags_row = ctx->fs_table;
+        table.taps_row = static_cast<float*>(ctx->fs_table);
+        at = 0;
+        for (size_t g = 0; g < members.size(); ++g) {
+            const int n = static_cast<int>(members[g].size());
+            if (n == 0) continue;
+            Prepared p;
+            p.sz = Sizing{};                                       // (the pads are the list's)
+            p.fx = find_fx_entry(8 * (pl.group_nkb[g] - 2));
+            p.mxt = &table;
+            p.mx_quirk = quirk;
+            const FwFrame* ft = static_cast<const FwFrame*>(ctx->fs_table) + at;
+            at += n;
+            int rc;
+            if constexpr (ffk) rc = run_ff<T>(ctx, d_src, d_dst, n, rows, cols, channels, p, fw_chsel_all(channels), L, ft);
+            else rc = channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, n, rows, cols, p, nullptr, fw_chsel_all(3), &L, ft)
+                                    : run_fc_u8(ctx, d_src, d_dst, n, rows, cols, channels, p, fw_chsel_all(channels), L, ft);
+            if (rc) return rc;
+        }
+    }
+    // the frames without a fused kernel, one by one on the plane path
+    blur_opts fft_opts;
+    blur_opts_default(&fft_opts);
+    if (opts) fft_opts = *opts;
+    fft_opts.engine = BLUR_ENGINE_FFT;
+    ChLayout L1 = L;
+    L1.sframe = L1.dframe = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const int s = pl.slot_of[f];
+        if (s < 0 || fused[s]) continue;
+        if (int rc = run_planes(ctx, src_of(f), dst_of(f), 1, rows, cols, channels, pl.slots[s].sigma, &fft_opts, L1)) return rc;
+        if (pn.count++ == 0) { pn.first = frame0 + f; pn.sigma = pl.slots[s].sigma; pn.why = why[s] ? why[s] : ""; }
+    }
+    if (!note) {
+        // family 6: every blurred frame ran on the fused kernel; 0: frames took the plane path, and the note names the first
+        ctx->last_family = pn.count ? 0 : 6;
+        ctx->engine_note.clear();
+        if (pn.count) {
+            char head[128];
+            std::snprintf(head, sizeof head, "%d frame%s on the plane path, the first frame %d (sigma %g)%s", pn.count, pn.count == 1 ? "" : "s", pn.first, pn.sigma,
+                          pn.why.empty() ? "" : ": ");
+            ctx->engine_note = head + pn.why;
+        }
+    }
+    return BLUR_OK;
+}
+
+// ======================================================================================
 // C ABI
 // ======================================================================================
 // ---- whole-image 2D path: helpers (the entry points are below, blur_pocketfft2d_*) ----
@@ -2569,6 +2884,9 @@ int blur_ctx_destroy(blur_ctx* ctx)
     if (ctx->ch_copy) (void)hipFree(ctx->ch_copy);
     if (ctx->ff_sums) (void)hipFree(ctx->ff_sums);
     if (ctx->ff_strips) (void)hipFree(ctx->ff_strips);
+    if (ctx->fs_table) (void)hipFree(ctx->fs_table);
+    if (ctx->fs_stage) (void)hipHostFree(ctx->fs_stage);
+    if (ctx->fs_uploaded) (void)hipEventDestroy(ctx->fs_uploaded);
     if (ctx->host_stage) (void)hipFree(ctx->host_stage);
     if (ctx->pipe.ready) {
         (void)hipStreamSynchronize(ctx->pipe.h2d);
@@ -2690,11 +3008,13 @@ static int run_mx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
 // chsel != 0 (blur_ch_sigmas_batch_impl: one sigma per channel): only these channels, on the one-channel-per-workgroup kernel of
 // the window class (Fw3Entry: whole-window strips)
 // lay (with chsel only; null: packed frames): the caller's layout, source and destination already disjoint
+// ft: the frame list of a launch over frames with their own sigmas (blur_ch_frame_sigmas_batch_impl; FwFrame), with chsel and a layout
 static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump = nullptr, FwChSel chsel = 0,
-                       const ChLayout* lay = nullptr)
+                       const ChLayout* lay = nullptr, const FwFrame* ft)
 {
     const size_t px = static_cast<size_t>(rows) * cols;
     if (lay && !chsel) return fail(ctx, BLUR_ERR_INVALID, "run_fx_u8c3: a layout goes with a channel selection");
+    if (ft && !lay) return fail(ctx, BLUR_ERR_INVALID, "run_fx_u8c3: a frame list goes with a layout");
     const FwPitch pt = lay ? fw_pitch_of(*lay) : fw_pitch_packed(rows, cols, 3, 1);
     // in place (the reference's own calling convention, Source.cpp:429,567): a strip reads its neighbours' columns and the rows
     // below while they are being written, so the frames are read from a copy in the workspace
@@ -2750,8 +3070,12 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
     FxQuirk qk{};
     if (!p.mx_quirk) {
         TimedLaunch t(ctx, 1, nframes);
-        hipLaunchKernelGGL(fx_prepass<1>, dim3(n_strip), dim3(256), 0, ctx->stream, d_src, nullptr, nullptr, nullptr, ctx->fx_strips, rows, cols, p.sz.pad, pada, 1, 1, 0, chunks_x,
-                           g.nright, strip_blocks, kFxSumRows, narrow, pt.src_pitch, pt.src_frame);
+        if (ft)
+            hipLaunchKernelGGL(fx_prepass_frames<1>, dim3(n_strip), dim3(256), 0, ctx->stream, d_src, nullptr, nullptr, nullptr, ctx->fx_strips, rows, cols, pada, 1, 1, 0,
+                               chunks_x, g.nright, strip_blocks, kFxSumRows, narrow, pt.src_pitch, pt.src_frame, ft);
+        else
+            hipLaunchKernelGGL(fx_prepass<1>, dim3(n_strip), dim3(256), 0, ctx->stream, d_src, nullptr, nullptr, nullptr, ctx->fx_strips, rows, cols, p.sz.pad, pada, 1, 1, 0,
+                               chunks_x, g.nright, strip_blocks, kFxSumRows, narrow, pt.src_pitch, pt.src_frame);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (p.mx_quirk) {
@@ -2775,8 +3099,13 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
         { TimedLaunch t(ctx, 1, nframes);
           const int n_alt = nbands * nbatches * nframes;
           auto kern = gpt == 1 ? fx_prepass<1> : (gpt == 2 ? fx_prepass<2> : fx_prepass<4>);
-          hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zpart, ctx->fx_strips, rows, cols, p.sz.pad, pada, nbands,
-                             nbatches, n_alt, chunks_x, g.nright, strip_blocks, band_rows, narrow, pt.src_pitch, pt.src_frame);
+          auto kern_frames = gpt == 1 ? fx_prepass_frames<1> : (gpt == 2 ? fx_prepass_frames<2> : fx_prepass_frames<4>);
+          if (ft)
+              hipLaunchKernelGGL(kern_frames, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zpart, ctx->fx_strips, rows, cols, pada, nbands, nbatches,
+                                 n_alt, chunks_x, g.nright, strip_blocks, band_rows, narrow, pt.src_pitch, pt.src_frame, ft);
+          else
+              hipLaunchKernelGGL(kern, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zpart, ctx->fx_strips, rows, cols, p.sz.pad, pada, nbands,
+                                 nbatches, n_alt, chunks_x, g.nright, strip_blocks, band_rows, narrow, pt.src_pitch, pt.src_frame);
           HIP_TRY(ctx, hipGetLastError()); }
         qk.srow_part = srow;
         qk.cpart = cpart;
@@ -2798,7 +3127,7 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
         const Fw3Entry* fe3 = find_fw3_entry(nkb);
         if (!fe3 || vdump || stamps) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for a subset of three channels: no kernel instantiated for this pad");
         TimedLaunch t(ctx, 0, nframes);
-        HIP_TRY(ctx, fe3->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel, pt));
+        HIP_TRY(ctx, fe3->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel, pt, ft));
         return BLUR_OK;
     }
     { TimedLaunch t(ctx, 0, nframes);
@@ -4015,6 +4344,51 @@ int blur_gaussian_bf16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d
 {
     const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
     return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+// one sigma per frame (blur_amd.h)
+int blur_gaussian_u8_frame_sigmas_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                            const blur_opts* opts)
+{
+    return blur_ch_frame_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_f32_frame_sigmas_batch_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                             const blur_opts* opts)
+{
+    return blur_ch_frame_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_u8_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint8_t* d_src, size_t src_pitch, size_t src_frame_stride, uint8_t* d_dst, size_t dst_pitch,
+                                                    size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_frame_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_f32_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst, size_t dst_pitch,
+                                                     size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_frame_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+// host-only: how a call with these sigmas groups its frames
+int blur_gaussian_frame_sigmas_plan(int rows, int cols, int nframes, const double* sigmas, int* out)
+{
+    FrameSigmaPlan pl;
+    int dummy = 0;
+    const char* why = nullptr;
+    if (!out) return BLUR_ERR_INVALID;
+    if (int rc = frame_sigmas_status(&dummy, &dummy, nframes, rows, cols, 1, sigmas, pl, &why)) return rc;
+    for (int f = 0; f < nframes; ++f) {
+        const int s = pl.slot_of[f];
+        out[4 * f] = s < 0 ? -1 : pl.slots[s].group;
+        out[4 * f + 1] = s < 0 ? 0 : pl.slots[s].sz.pad;
+        out[4 * f + 2] = s < 0 ? 0 : pl.slots[s].nkb;
+        out[4 * f + 3] = s;
+    }
+    return BLUR_OK;
 }
 
 // u8 images, one sigma per channel

@@ -149,7 +149,8 @@ __device__ __forceinline__ void ff_quirk_cols_tile(unsigned char* scratch, float
 // One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
 template <typename T, int NKB, bool QUIRK, int CH>
 __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
-                                                  int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips, FwChSel chsel, FwPitch pt)
+                                                  int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips, FwChSel chsel, FwPitch pt,
+                                                  const FwFrame* __restrict__ ft)
 {
     static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
     static_assert(ff_is_pixel_v<T>, "float32, u16, float16 or bfloat16 pixels");
@@ -171,9 +172,22 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
     const int xc = (task / nact) % chunks, seg = (task / (nact * chunks)) % nseg, f = task / (nact * chunks * nseg);
     const int x0 = xc * kFxChunk;
     const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
+    // a launch over frames with their own sigmas (FwFrame, fw_kernels.hpp): everything below that depends on sigma is replaced here,
+    // once.  (mbits, like the sums and the strips, is the group's pre-pass's: indexed by the position f in the list)
+    int fr = f;
+    if (ft) {
+        const FwFrame e = ft[f];
+        fr = e.frame;
+        g.pad = e.pad;
+        frags += e.frags;
+        qk.taps += e.taps;
+        qk.dr = e.dr;
+        qk.dc = e.dc;
+        qk.bscale = e.bscale;
+    }
     // (FwPitch, fw_kernels.hpp: pitches and frame strides in bytes, multiples of the sample's size)
-    const T* img = reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(src) + static_cast<size_t>(f) * pt.src_frame);
-    T* out = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(dst) + static_cast<size_t>(f) * pt.dst_frame);
+    const T* img = reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(src) + static_cast<size_t>(fr) * pt.src_frame);
+    T* out = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(dst) + static_cast<size_t>(fr) * pt.dst_frame);
 
     // the frame's scale (ff_scale_exp): s = 2^e on the staged values, 2^-e on the results (u16: from the type's range, mbits is not read)
     const int sexp = U16 ? ff_scale_exp(65535.f, qk.bscale) : ff_scale_exp(__uint_as_float(qk.mbits[f]), qk.bscale);
@@ -499,9 +513,10 @@ __host__ __device__ constexpr bool ff_class_in_contract(int nkb) { return nkb <=
 template <typename T> struct FfEntryT {
     int nkb;
     // ch: 1, 3 or 4; quirk: whether the quirk's sums in qk are there (float and the half types: qk.mbits always is; u16: never read);
-    // chsel: the channels to blur; pt: where the rows and frames lie (FwPitch)
+    // chsel: the channels to blur; pt: where the rows and frames lie (FwPitch); ft: the frame list of a launch over frames with their
+    // own sigmas, or null (FwFrame)
     hipError_t (*blur)(hipStream_t, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk, const T* strips,
-                       FwChSel chsel, FwPitch pt);
+                       FwChSel chsel, FwPitch pt, const FwFrame* ft);
 };
 using FfEntry = FfEntryT<float>;
 using FfEntryU16 = FfEntryT<uint16_t>;
@@ -509,7 +524,7 @@ using FfEntryF16 = FfEntryT<ff_f16>;
 using FfEntryBf16 = FfEntryT<ff_bf16>;
 
 template <typename T, int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int num_cus, const FfQuirk& qk,
-                                                               bool quirk, const T* strips, FwChSel chsel, FwPitch pt)
+                                                               bool quirk, const T* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
 {
     using C = FfCfg<NKB, ff_is_half_v<T> ? 1 : 2>;
     const int nact = fw_chsel_count(chsel);
@@ -523,20 +538,20 @@ template <typename T, int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, c
     if (e != hipSuccess) return e;
     if (quirk)
         hipLaunchKernelGGL((ff_blur<T, NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel, pt);
+                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel, pt, ft);
     else
         hipLaunchKernelGGL((ff_blur<T, NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel, pt);
+                           l.nseg, static_cast<int>(l.ntasks), qk, strips, chsel, pt, ft);
     return hipGetLastError();
 }
 
 template <typename T, int NKB> hipError_t ff_launch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk,
-                                                    bool quirk, const T* strips, FwChSel chsel, FwPitch pt)
+                                                    bool quirk, const T* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
 {
-    if (ch == 1) return ff_launch_ch<T, NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt);
+    if (ch == 1) return ff_launch_ch<T, NKB, 1>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt, ft);
     if constexpr (ff_class_ok_t<T>(NKB, 3)) {
-        if (ch == 3) return ff_launch_ch<T, NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt);
-        if (ch == 4) return ff_launch_ch<T, NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt);
+        if (ch == 3) return ff_launch_ch<T, NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt, ft);
+        if (ch == 4) return ff_launch_ch<T, NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt, ft);
     }
     return hipErrorInvalidValue;
 }
@@ -731,9 +746,33 @@ __global__ __launch_bounds__(256) void ff_prepass(const T* __restrict__ src, uns
     }
 }
 
+// ff_prepass for a launch over frames with their own sigmas (FwFrame, fw_kernels.hpp: fc_prepass_frames): workgroup frame f of the
+// grid is entry f of the list `ft`, the sums are weighted with that frame's pad and read its frame of the source
+template <typename T, int CH, int G>
+__global__ __launch_bounds__(256) void ff_prepass_frames(const T* __restrict__ src, unsigned* __restrict__ mbits, double* __restrict__ spart, double* __restrict__ cpart,
+                                                         T* __restrict__ strips, int rows, int cols, int pada, int nbands, int nbatches, int cpitch, int n_alt,
+                                                         int chunks, int nright, int strip_blocks, int band_rows, int sums, uint32_t spitch, size_t sframe,
+                                                         const FwFrame* __restrict__ ft)
+{
+    int b = blockIdx.x;
+    const bool alt = b < n_alt;
+    if (!alt) b -= n_alt;
+    const int nstrips = fx_left_strips(pada) + nright;
+    const int f = alt ? b / (nbands * nbatches) : b / (strip_blocks * nstrips);
+    // (the bodies address the source as src + f sframe: the frame's own offset less that)
+    const T* s = reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(src) + (static_cast<ptrdiff_t>(ft[f].frame) - f) * static_cast<ptrdiff_t>(sframe));
+    if (alt) {
+        const int band = b % nbands, batch = (b / nbands) % nbatches;
+        ff_altsums_body<T, CH, G>(s, mbits, spart, cpart, rows, cols, ft[f].pad, nbands, nbatches, cpitch, band, batch, f, band_rows, sums != 0, spitch, sframe);
+    } else {
+        const int bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips;
+        ff_edge_strips_body<T, CH>(s, strips, rows, cols, pada, chunks, nright, bx, sidx, f, spitch, sframe);
+    }
+}
+
 // Srow complete (the batches' parts in order) and Z = sum_r wy(r) Srow(r) (a fixed tree): one workgroup per frame
 template <int CH>
-__global__ __launch_bounds__(256) void ff_finalize(const double* __restrict__ spart, double* __restrict__ srow, double* __restrict__ zsum, int rows, int pad, int nbatches)
+__device__ __forceinline__ void ff_finalize_body(const double* __restrict__ spart, double* __restrict__ srow, double* __restrict__ zsum, int rows, int pad, int nbatches)
 {
     __shared__ double zr[CH][256];
     const int tid = threadIdx.x, f = blockIdx.x;
@@ -760,6 +799,18 @@ __global__ __launch_bounds__(256) void ff_finalize(const double* __restrict__ sp
         __syncthreads();
     }
     if (tid < CH) zsum[static_cast<size_t>(f) * CH + tid] = zr[tid][0];
+}
+template <int CH>
+__global__ __launch_bounds__(256) void ff_finalize(const double* __restrict__ spart, double* __restrict__ srow, double* __restrict__ zsum, int rows, int pad, int nbatches)
+{
+    ff_finalize_body<CH>(spart, srow, zsum, rows, pad, nbatches);
+}
+// the same with the pad of the workgroup's frame from the list of a launch over frames with their own sigmas
+template <int CH>
+__global__ __launch_bounds__(256) void ff_finalize_frames(const double* __restrict__ spart, double* __restrict__ srow, double* __restrict__ zsum, int rows, int nbatches,
+                                                          const FwFrame* __restrict__ ft)
+{
+    ff_finalize_body<CH>(spart, srow, zsum, rows, ft[blockIdx.x].pad, nbatches);
 }
 
 }  // namespace blur_amd

@@ -28,6 +28,7 @@
 //     ones beyond NKB holding only vector work.
 #pragma once
 #include "fx_kernels.hpp"
+#include <cstddef>
 #include <type_traits>
 
 #ifndef FW_TL_REGS
@@ -73,6 +74,22 @@ inline FwPitch fw_pitch_packed(int rows, int cols, int ch, int es)
     const uint32_t pitch = static_cast<uint32_t>(cols) * static_cast<uint32_t>(ch * es);
     return FwPitch{ pitch, pitch, static_cast<size_t>(rows) * pitch, static_cast<size_t>(rows) * pitch };
 }
+
+// One frame of a launch over frames that each have their own sigma (blur_gaussian_*_frame_sigmas_*: the frames of one window class
+// share a launch).  The launch's frame list `ft` has one entry per task frame; a null list is a launch with one sigma, whose pad,
+// fragments, taps and gains are the launch-wide arguments.  The kernels read the entry once, in the prologue, with scalar loads (the
+// task's frame is uniform); the step loop knows the window class only.  Position f in the list indexes everything the group's
+// pre-pass made (strips, the quirk's sums, max|x|); `frame` is the frame's index in the call and addresses the source and destination.
+// The fragments and taps of every frame of a call lie in one table: `frags` (in mx_half8) and `taps` (in floats) count from its start,
+// which the launch passes where a launch with one sigma passes the fragments and the taps.
+struct FwFrame {
+    int frame;
+    int pad;
+    uint32_t frags, taps;
+    float dr, dc;               // the quirk's gains for this sigma (FcQuirk, FxQuirk, FfQuirk)
+    double bscale;              // float frames: B of ff_scale_exp (FfQuirk)
+};
+static_assert(sizeof(FwFrame) == 32, "eight dwords: one scalar load");
 
 template <int NKB> struct FwCfg {
     static constexpr int PADA = 8 * (NKB - 2), WIN = kFxChunk + 2 * PADA, GPR = WIN / 4, PER = (GPR + 7) / 8;
@@ -158,9 +175,16 @@ __device__ __forceinline__ void fc_quirk_cols_tile(unsigned char* scratch, float
 }
 
 // One workgroup per (frame, segment of output tiles, chunk of 128 pixel columns, channel), channel fastest.
-template <int NKB, bool QUIRK, int CH>
+// FRAMES: a launch over frames with their own sigmas (FwFrame), its list in `ft`; without, `ft` is an empty argument and the kernel
+// is the one it was.  Two instantiations and not one kernel with a nullable list (as ff_blur has it, at no cost): that form cost the
+// quirk instantiations here 1 .. 10 more spilled scalar registers each (they sit at the limit of 106 with 25 .. 32 spilled), and so
+// did a shared inlined body under two kernels.
+struct FwNoFrames {};
+template <bool FRAMES> using FwFrameList = std::conditional_t<FRAMES, const FwFrame*, FwNoFrames>;
+template <int NKB, bool QUIRK, int CH, bool FRAMES = false>
 __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const mx_half8* __restrict__ frags, FxGeom g,
-                                                     int chunks, int tps, int nseg, int ntasks, FwQuirk<CH> qk, const uint8_t* __restrict__ strips, FwChSel chsel, FwPitch pt)
+                                                     int chunks, int tps, int nseg, int ntasks, FwQuirk<CH> qk, const uint8_t* __restrict__ strips, FwChSel chsel, FwPitch pt,
+                                                     FwFrameList<FRAMES> ft)
 {
     static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
     using C = FwCfg<NKB>;
@@ -178,8 +202,19 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
     const int xc = (task / nact) % chunks, seg = (task / (nact * chunks)) % nseg, f = task / (nact * chunks * nseg);
     const int x0 = xc * kFxChunk;
     const int tile0 = seg * tps, tile1 = min(tile0 + tps, g.ntiles);
-    const uint8_t* img = src + static_cast<size_t>(f) * pt.src_frame;
-    uint8_t* out = dst + static_cast<size_t>(f) * pt.dst_frame;
+    // a launch over frames with their own sigmas (FwFrame): everything below that depends on sigma is replaced here, once
+    int fr = f;
+    if constexpr (FRAMES) {
+        const FwFrame e = ft[f];
+        fr = e.frame;
+        g.pad = e.pad;
+        frags += e.frags;
+        qk.taps += e.taps;
+        qk.dr = e.dr;
+        qk.dc = e.dc;
+    }
+    const uint8_t* img = src + static_cast<size_t>(fr) * pt.src_frame;
+    uint8_t* out = dst + static_cast<size_t>(fr) * pt.dst_frame;
 
     // fragments: hi halves in registers; of the lo halves the first TLR in registers too, the rest in LDS (the row pass reads a
     // window fragment per block already: with every lo half from LDS as well its two products would wait for the LDS pipe)
@@ -521,8 +556,9 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
     }
 }
 
+// ft: the launch's frame list (device; g.nframes entries) or null (FwFrame)
 template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FwQuirk<CH>* qk,
-                                               const uint8_t* strips, FwChSel chsel, FwPitch pt)
+                                               const uint8_t* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
 {
     using C = FwCfg<NKB>;
     const int nact = fw_chsel_count(chsel);
@@ -532,14 +568,18 @@ template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* s
     const FxLaunch l = fx_plan_launch(g, nact, C::NT, num_cus);
     if (l.ntasks == 0) return hipSuccess;
     static std::atomic<unsigned long long> attr_done{ 0 };
-    const hipError_t e = fx_set_lds(attr_done, C::LDS, fw_blur_u8<NKB, true, CH>, fw_blur_u8<NKB, false, CH>);
+    const hipError_t e = fx_set_lds(attr_done, C::LDS, fw_blur_u8<NKB, true, CH>, fw_blur_u8<NKB, false, CH>, fw_blur_u8<NKB, true, CH, true>,
+                                    fw_blur_u8<NKB, false, CH, true>);
     if (e != hipSuccess) return e;
-    if (qk)
-        hipLaunchKernelGGL((fw_blur_u8<NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), *qk, strips, chsel, pt);
-    else
-        hipLaunchKernelGGL((fw_blur_u8<NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, static_cast<const mx_half8*>(frags), g, l.chunks, l.tps,
-                           l.nseg, static_cast<int>(l.ntasks), FwQuirk<CH>{}, strips, chsel, pt);
+    const mx_half8* fr = static_cast<const mx_half8*>(frags);
+    const int nt = static_cast<int>(l.ntasks);
+    if (ft) {
+        if (qk) hipLaunchKernelGGL((fw_blur_u8<NKB, true, CH, true>), l.grid, dim3(256), C::LDS, st, src, dst, fr, g, l.chunks, l.tps, l.nseg, nt, *qk, strips, chsel, pt, ft);
+        else hipLaunchKernelGGL((fw_blur_u8<NKB, false, CH, true>), l.grid, dim3(256), C::LDS, st, src, dst, fr, g, l.chunks, l.tps, l.nseg, nt, FwQuirk<CH>{}, strips, chsel, pt, ft);
+    } else {
+        if (qk) hipLaunchKernelGGL((fw_blur_u8<NKB, true, CH>), l.grid, dim3(256), C::LDS, st, src, dst, fr, g, l.chunks, l.tps, l.nseg, nt, *qk, strips, chsel, pt, FwNoFrames{});
+        else hipLaunchKernelGGL((fw_blur_u8<NKB, false, CH>), l.grid, dim3(256), C::LDS, st, src, dst, fr, g, l.chunks, l.tps, l.nseg, nt, FwQuirk<CH>{}, strips, chsel, pt, FwNoFrames{});
+    }
     return hipGetLastError();
 }
 
@@ -548,14 +588,15 @@ template <int NKB> hipError_t fw_launch_u8c3(hipStream_t st, const uint8_t* src,
                                              const uint8_t* strips, float* vdump, unsigned long long* stamps)
 {
     if (vdump || stamps) return hipErrorNotSupported;            // the row-pass dump and the phase stamps are builds of fx_blur_u8 only
-    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, fw_chsel_all(3), fw_pitch_packed(g.rows, g.cols, 3, 1));
+    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, fw_chsel_all(3), fw_pitch_packed(g.rows, g.cols, 3, 1), nullptr);
 }
 
 struct FcEntry {
     int nkb;
-    // ch: 1 or 4; qk: the quirk's sums (null: nyquist_quirk = 0); chsel: the channels to blur; pt: where the rows and frames lie
+    // ch: 1 or 4; qk: the quirk's sums (null: nyquist_quirk = 0); chsel: the channels to blur; pt: where the rows and frames lie;
+    // ft: the frame list of a launch over frames with their own sigmas, or null (FwFrame)
     hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk, const uint8_t* strips,
-                          FwChSel chsel, FwPitch pt);
+                          FwChSel chsel, FwPitch pt, const FwFrame* ft);
 };
 
 // three channels, a subset of them per launch (one sigma per channel), every window class: the strips are whole windows (fx_prepass
@@ -563,20 +604,20 @@ struct FcEntry {
 struct Fw3Entry {
     int nkb;
     hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk, const uint8_t* strips, FwChSel chsel,
-                          FwPitch pt);
+                          FwPitch pt, const FwFrame* ft);
 };
 template <int NKB> hipError_t fw_launch_u8c3_sel(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk,
-                                                 const uint8_t* strips, FwChSel chsel, FwPitch pt)
+                                                 const uint8_t* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
 {
-    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt);
+    return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
 }
 
 // the one- and four-channel entry (FcEntry; fx_registry.hpp: find_fc_entry) of every window class
 template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk,
-                                              const uint8_t* strips, FwChSel chsel, FwPitch pt)
+                                              const uint8_t* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
 {
-    if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt);
-    if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt);
+    if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
+    if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
     return hipErrorInvalidValue;
 }
 
@@ -734,5 +775,51 @@ __global__ __launch_bounds__(256) void fc_prepass(const uint8_t* __restrict__ sr
         fc_edge_strips_body<CH>(src, strips, rows, cols, pada, chunks, nright, bx, sidx, f, spitch, sframe);
     }
 }
+
+// fc_prepass for a launch over frames with their own sigmas: workgroup frame f of the grid is entry f of the list `ft`; the sums are
+// weighted with that frame's pad and read its frame of the source (the outputs are indexed by f, as the fused launch reads them)
+template <int CH, int G>
+__global__ __launch_bounds__(256) void fc_prepass_frames(const uint8_t* __restrict__ src, int* __restrict__ srow, int* __restrict__ cpart, long long* __restrict__ zsum,
+                                                         uint8_t* __restrict__ strips, int rows, int cols, int pada, int nbands, int nbatches, int cpitch, int n_alt,
+                                                         int chunks, int nright, int strip_blocks, int band_rows, unsigned chmask, uint32_t spitch, size_t sframe,
+                                                         const FwFrame* __restrict__ ft)
+{
+    __shared__ int sred[kFcSumRows][CH][64];
+    int b = blockIdx.x;
+    if (b < n_alt) {
+        const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
+        // (the bodies address the source as src + f sframe: the frame's own offset less that)
+        const uint8_t* s = src + (static_cast<ptrdiff_t>(ft[f].frame) - f) * static_cast<ptrdiff_t>(sframe);
+        fc_altsums_body<CH, G>(s, srow, cpart, zsum, rows, cols, ft[f].pad, nbands, cpitch, band, batch, f, sred, band_rows, chmask, spitch, sframe);
+    } else {
+        b -= n_alt;
+        const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);
+        const uint8_t* s = src + (static_cast<ptrdiff_t>(ft[f].frame) - f) * static_cast<ptrdiff_t>(sframe);
+        fc_edge_strips_body<CH>(s, strips, rows, cols, pada, chunks, nright, bx, sidx, f, spitch, sframe);
+    }
+}
+
+#ifdef BLUR_FX_QUIRK_KERNELS
+// fx_prepass (three channels: fx_kernels.hpp) for a launch over frames with their own sigmas, as fc_prepass_frames
+template <int G>
+__global__ __launch_bounds__(256) void fx_prepass_frames(const uint8_t* __restrict__ src, int* __restrict__ srow_part, int* __restrict__ cpart, long long* __restrict__ zpart,
+                                                         uint8_t* __restrict__ strips, int rows, int cols, int pada, int nbands, int nbatches, int n_alt, int chunks,
+                                                         int nright, int strip_blocks, int band_rows, int narrow, uint32_t spitch, size_t sframe,
+                                                         const FwFrame* __restrict__ ft)
+{
+    __shared__ int sred[kFxSumRows][3][64];
+    int b = blockIdx.x;
+    if (b < n_alt) {
+        const int band = b % nbands, batch = (b / nbands) % nbatches, f = b / (nbands * nbatches);
+        const uint8_t* s = src + (static_cast<ptrdiff_t>(ft[f].frame) - f) * static_cast<ptrdiff_t>(sframe);
+        fx_altsums_body<G>(s, srow_part, cpart, zpart, rows, cols, ft[f].pad, nbands, nbatches, band, batch, f, sred, band_rows, spitch, sframe);
+    } else {
+        b -= n_alt;
+        const int nstrips = fx_left_strips(pada) + nright, bx = b % strip_blocks, sidx = (b / strip_blocks) % nstrips, f = b / (strip_blocks * nstrips);
+        const uint8_t* s = src + (static_cast<ptrdiff_t>(ft[f].frame) - f) * static_cast<ptrdiff_t>(sframe);
+        fx_edge_strips_body(s, strips, rows, cols, pada, chunks, nright, bx, sidx, f, narrow, spitch, sframe);
+    }
+}
+#endif  // BLUR_FX_QUIRK_KERNELS
 
 }  // namespace blur_amd

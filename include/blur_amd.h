@@ -541,6 +541,55 @@ int blur_gaussian_bf16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d
    pad has no fused kernel (pad > 168).  Status as the entries above; BLUR_ERR_INVALID also for a null `out`. */
 int blur_gaussian_sigmas_plan(int rows, int cols, int channels, const double* sigmas, int* out);
 
+/* ---- one sigma per frame, DEVICE pointers -------------------------------------------------------------------------------------
+   The _frame_sigmas_ entries take `const double sigmas[nframes]` (HOST memory) where the batch entries take `double sigma`: an
+   augmentation that draws a sigma per image of a training batch, a clip whose blur changes from frame to frame, or (pitched entry,
+   src_frame_stride = 0) one frame blurred with K sigmas into K outputs.  u8 and float32, channels in {1, 3, 4}.
+     sigmas[f] > 0   frame f of the result is, bit for bit, what the scalar entry of the same type returns for that frame alone with
+                     sigma = sigmas[f] and the same opts (a float32 frame's power-of-two scale comes from its own max|x|).  The one
+                     exception is u8 with three channels, where the scalar call runs its own three-channel kernels: such a frame
+                     runs on the one-channel-per-workgroup kernel (the route of the _sigmas_ and pitched entries) and meets the same
+                     float64 oracle under the same tie rule.  Three-channel u8 frames are NEVER forwarded to the u8c3 entry, not even
+                     when every sigma is equal: a frame's bytes depend on its pixels, its sigma and opts only -- not on its position
+                     in the batch, on the other frames, or on whether it is blurred alone.  (A caller with ONE sigma for all of its
+                     BGR frames should call the scalar entry: its kernel is faster for narrow windows, pad <= 72.)
+     sigmas[f] == 0  frame f is copied bit for bit; an in-place call does not touch it.
+   Cost: the frames are grouped by the fused kernel's window class (NKB = 3, 5 .. 23: pad <= 8 (NKB - 2)) and every class is ONE
+   pre-pass and ONE fused launch over its frames, whatever their sigmas: at most 11 fused launches per call where the loop over the
+   scalar entry has one per frame.  The fragments and taps of the call's sigmas are built on the host and uploaded once per call
+   into a workspace of the context; nothing is cached per sigma, so a stream of never-repeating sigmas costs no device memory.
+   opts->engine applies per frame: AUTO gives a frame the fused kernel wherever the scalar entry's rules give it to that sigma (u8
+   with three channels: wherever the 1- and 4-channel rules do) and the f32 plane path elsewhere, one frame at a time; FUSED fails
+   with BLUR_ERR_UNSUPPORTED, before anything is written, if any frame has no fused kernel; FFT takes the plane path for every
+   frame.  After the call blur_last_engine returns family 6 if every blurred frame ran on the fused kernel and 0 otherwise; the note
+   then says how many frames took the plane path and names the first of them, its sigma and the reason.
+   BLUR_ERR_INVALID: channels not in {1, 3, 4}, a NULL pointer (sigmas included), nframes < 0, rows or cols <= 0, a negative, NaN or
+   infinite sigma; BLUR_ERR_UNSUPPORTED: a frame whose pad exceeds min(rows, cols) - 1.  Every entry of sigmas is checked before the
+   device is touched (ctx may then be NULL) and before anything is written; nframes == 0 is a no-op.
+   Pitched entries: the rules of blur_gaussian_*_pitched_batch_dev, and src_frame_stride == 0 is accepted for any nframes: every
+   frame of the result is blurred from the same source frame (scale space, difference of Gaussians).  A dst_frame_stride of 0 with
+   nframes > 1 stays BLUR_ERR_INVALID.  Stores are masked by x < cols; overlapping source and destination spans, in place
+   included, are read from one gathered copy (a large in-place batch in parts of 1 GiB).
+   Asynchronous on the context's stream as far as the kernels go; the call keeps the host busy while it builds and uploads its
+   tables.  sigmas is read before the call returns. */
+int blur_gaussian_u8_frame_sigmas_batch_dev(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, int channels,
+                                            const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f32_frame_sigmas_batch_dev(blur_ctx* ctx, const float* d_src, float* d_dst, int nframes, int rows, int cols, int channels,
+                                             const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u8_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint8_t* d_src, size_t src_pitch, size_t src_frame_stride, uint8_t* d_dst,
+                                                    size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                                    const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f32_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst,
+                                                     size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                                     const double* sigmas, const blur_opts* opts);
+/* host-only plan of the calls above (no GPU needed; the same host code the entries use): for frame f, out[4 f] = its launch group
+   (the frames of one window class share an index, counted in the order of their first frame; -1 for sigma = 0), out[4 f + 1] = the
+   pad of its sigma, out[4 f + 2] = the fused kernel's window class NKB, 8 (NKB - 4) < pad <= 8 (NKB - 2), or 0 where the pad has no
+   fused kernel (pad > 168; these frames form a group of their own), out[4 f + 3] = its table slot (frames of equal sigma share
+   one, counted in the order of their first frame; -1 for sigma = 0).  Status as the entries above; BLUR_ERR_INVALID also for a null
+   `out`. */
+int blur_gaussian_frame_sigmas_plan(int rows, int cols, int nframes, const double* sigmas, int* out);
+
 /* fastboxblur over a batch, sharded by frame exactly like the two calls above, in place (blur_fastboxblur_u8_batch_dev on
    each shard); arguments and errors as blur_fastboxblur_u8_batch_dev, nframes == 0 is a no-op, shards without frames idle. */
 int blur_fastboxblur_u8_batch_multi_dev(blur_multi* m, uint8_t* d_inout, int nframes, int w, int h, int channels,

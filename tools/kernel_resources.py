@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Registers, spills and scratch of every kernel in hipcc objects, from the code-object metadata (no GPU needed).
+
+    tools/kernel_resources.py DIR_OR_OBJECT...            one line per kernel
+    tools/kernel_resources.py --diff BASE_DIR NEW_DIR [STRIP]
+                                                          kernels whose figures differ between two builds, and every kernel that
+                                                          gained a spill or scratch (exit status 1 then).  STRIP: a regular
+                                                          expression for the pieces of the mangled names to leave out when the
+                                                          builds are matched (a parameter that one build added: PKNS_7FwFrameE)
+"""
+import glob
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
+FIELDS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size")
+
+
+def kernels(obj, arch="gfx950"):
+    """{kernel name: (vgpr, agpr, sgpr, vgpr spills, sgpr spills, scratch bytes)} of one host object with an embedded code object"""
+    with tempfile.TemporaryDirectory() as tmp:
+        fb, co = os.path.join(tmp, "a.hipfb"), os.path.join(tmp, "a.co")
+        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(tmp, "copy.o")])
+        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--" + arch,
+                               "--input=" + fb, "--output=" + co])
+        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
+    out = {}
+    for block in re.split(r"\n\s*- \.agpr_count:", "\n" + notes)[1:]:
+        block = "    - .agpr_count:" + block
+        name = re.search(r"\.name:\s+(\S+)", block)
+        if not name:
+            continue
+        vals = []
+        for f in FIELDS:
+            m = re.search(re.escape(f) + r":\s+(\d+)", block)
+            vals.append(int(m.group(1)) if m else 0)
+        out[name.group(1)] = tuple(vals)
+    return out
+
+
+def objects(path):
+    return sorted(glob.glob(os.path.join(path, "*.o"))) if os.path.isdir(path) else [path]
+
+
+def main(argv):
+    if argv and argv[0] == "--diff":
+        base, new, strip = argv[1], argv[2], argv[3] if len(argv) > 3 else None
+        worse = changed = total = 0
+        for o in objects(new):
+            b = os.path.join(base, os.path.basename(o))
+            if not os.path.exists(b):
+                continue
+            try:
+                kn, kb = kernels(o), kernels(b)
+                if strip:
+                    kn = {re.sub(strip, "", k): v for k, v in kn.items()}
+                    kb = {re.sub(strip, "", k): v for k, v in kb.items()}
+            except subprocess.CalledProcessError:
+                continue                                  # no device code in this object
+            for name, v in sorted(kn.items()):
+                total += 1
+                w = kb.get(name)
+                if w is None:
+                    print("unmatched", os.path.basename(o), name)
+                    continue
+                if w == v:
+                    continue
+                changed += 1
+                bad = v[3] > w[3] or v[4] > w[4] or v[5] > w[5]
+                worse += bad
+                print("%s %s %s: vgpr/agpr/sgpr/vspill/sspill/scratch %s -> %s" % ("WORSE " if bad else "differs", os.path.basename(o), name, w, v))
+        print("%d kernels compared, %d differ, %d gained a spill or scratch" % (total, changed, worse))
+        return 1 if worse else 0
+    for path in argv:
+        for o in objects(path):
+            try:
+                for name, v in sorted(kernels(o).items()):
+                    print(os.path.basename(o), name, *v)
+            except subprocess.CalledProcessError:
+                pass
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
