@@ -35,8 +35,9 @@
 #include "fft_engine.hpp"
 #include "host_math.hpp"
 #define BLUR_MX_QUIRK_KERNELS
-#include "mx_registry.hpp"
+#include "mx_kernels.hpp"
 #define BLUR_FX_QUIRK_KERNELS
+#include "fw_kernels.hpp"
 #include "fx_registry.hpp"
 #include "bx_box.hpp"
 #include "wr_registry.hpp"
@@ -1515,7 +1516,7 @@ static int prepare(blur_ctx* ctx, int rows, int cols, double sigma, const blur_o
     // frame inside a batch give the same bytes.
     bool small_fft = false;
     if (choice == 0) {
-        const MxEntry* me0 = find_mx_entry(p.sz.pad);
+        const MxEntry* me0 = find_entry_for_pad<MxEntry>(p.sz.pad);
         // (wide: measured on 4K frames only; the 1.5-3.8 MP images of the reference's sweep with sigma 39-49 run 1.0-1.5 times
         // FASTER on the matrix cores than on the wave-resident FFT kernels, so the rule is limited to large frames)
         const bool small = static_cast<long long>(rows) * cols < 1000000ll, wide = me0 && me0->nkb >= 19 && static_cast<long long>(rows) * cols >= 6000000ll;
@@ -1526,7 +1527,7 @@ static int prepare(blur_ctx* ctx, int rows, int cols, double sigma, const blur_o
     }
     const bool force_tiled = opts && opts->tile_points > 0;       // (tests: straight to the tiled wave-resident path)
     if (!force_tiled && allow_fast && allow_wr && (choice == BLUR_ENGINE_FUSED || choice == BLUR_ENGINE_AUTO)) {
-        const FxEntry* fe = find_fx_entry(p.sz.pad);
+        const FxEntry* fe = find_entry_for_pad<FxEntry>(p.sz.pad);
         // the one-channel-per-workgroup kernels for wide windows (fw_kernels.hpp; measured against the two-kernel engine / the FFT
         // kernels, GP/s: 4K sigma 30 single frame 61 / 50 / 57, eight frames 98 / 85 / 70; 8K sigma 40 single 79 / 54 / 26;
         // 1080p sigma 30 single 29 / 31 / 36, eight 68 / 63 / 59; 1000 x 1500 sigma 38.7 single 17 / 21 / 13; 4K sigma 50 single
@@ -1556,7 +1557,7 @@ static int prepare(blur_ctx* ctx, int rows, int cols, double sigma, const blur_o
         }
     }
     if (!force_tiled && allow_fast && allow_wr && !small_fft && (choice == 0 || choice == 3)) {
-        const MxEntry* me = find_mx_entry(p.sz.pad);
+        const MxEntry* me = find_entry_for_pad<MxEntry>(p.sz.pad);
         const int vpitch = (3 * cols + 31) & ~31;
         const bool fits = me && static_cast<long long>(mx_vrows(rows, me->nkb)) * vpitch < (1ll << 30) && static_cast<long long>(rows) * cols * 3 < (1ll << 32);
         if (!fits && choice != 0)
@@ -1744,9 +1745,9 @@ static int run_colpass_u8c3(blur_ctx* ctx, const float* planes, uint8_t* dst, in
 // (blur_gaussian_f32_*, blur_gaussian_u16_*, blur_gaussian_f16_*, blur_gaussian_bf16_*): every channel blurred on its own as pffft_()
 // blurs one of its planes (u8 and u16 with the + 0.5f truncation, float32 without, the half types rounded once to nearest even)
 // ======================================================================================
-#include "ff_registry.hpp"
+#include "ff_kernels.hpp"
 
-// the per-channel entries' pixel types by name (messages), and the fused kernel of a window class by type
+// the per-channel entries' pixel types by name (messages)
 template <typename T> constexpr const char* ch_type_name()
 {
     if constexpr (std::is_same_v<T, uint16_t>) return "u16";
@@ -1754,13 +1755,6 @@ template <typename T> constexpr const char* ch_type_name()
     else if constexpr (std::is_same_v<T, ff_bf16>) return "bfloat16";
     else if constexpr (std::is_same_v<T, float>) return "float32";
     else return "u8";
-}
-template <typename T> static const FfEntryT<T>* find_ff_entry_t(int nkb)
-{
-    if constexpr (std::is_same_v<T, uint16_t>) return find_ff_u16_entry(nkb);
-    else if constexpr (std::is_same_v<T, ff_f16>) return find_ff_f16_entry(nkb);
-    else if constexpr (std::is_same_v<T, ff_bf16>) return find_ff_bf16_entry(nkb);
-    else return find_ff_entry(nkb);
 }
 
 static int ensure_buf(blur_ctx* ctx, void** buf, size_t* have, size_t bytes)
@@ -1809,7 +1803,7 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
 {
     const FwPitch pt = fw_pitch_of(L);
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
-    const FcEntry* fe = find_fc_entry(nkb);
+    const FcEntry* fe = find_entry<FcEntry>(nkb);
     if (!fe) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for 1 / 4 channels: no kernel instantiated for this pad");
     FxGeom g{ rows, cols, p.sz.pad, nframes, 0, (rows + 31) / 32, fx_right_strips(cols, pada), ctx->num_xcds };
     const int chunks_x = (cols + kFxChunk - 1) / kFxChunk, win = kFxChunk + 2 * pada, nstrips = fx_left_strips(pada) + g.nright;
@@ -1876,7 +1870,7 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
     const FwPitch pt = fw_pitch_of(L);
     constexpr bool u16 = std::is_same_v<T, uint16_t>;
     const int nkb = p.fx->nkb, pada = 8 * (nkb - 2);
-    const FfEntryT<T>* fe = find_ff_entry_t<T>(nkb);
+    const FfEntryT<T>* fe = find_entry<FfEntryT<T>>(nkb);
     if (!fe || !ff_class_ok_t<T>(nkb, ch))
         return fail(ctx, BLUR_ERR_UNSUPPORTED, (std::string("fused kernel for ") + ch_type_name<T>() + " images: no kernel instantiated for this pad and channel count").c_str());
     FxGeom g{ rows, cols, p.sz.pad, nframes, 0, (rows + 31) / 32, fx_right_strips(cols, pada), ctx->num_xcds };
@@ -2514,7 +2508,7 @@ static int frame_sigmas_status(const void* src, const void* dst, int nframes, in
             FrameSigmaPlan::Slot sl{ sigmas[f], pffft_sizing(rows, cols, sigmas[f]), 0, 0 };
             if (sl.sz.pad > rows - 1 || sl.sz.pad > cols - 1)
                 return no(BLUR_ERR_UNSUPPORTED, "pad > min(rows, cols) - 1 for one of the sigmas: reflect-101 would read outside the image (README.md:33-38)");
-            const FxEntry* fe = find_fx_entry(sl.sz.pad);
+            const FxEntry* fe = find_entry_for_pad<FxEntry>(sl.sz.pad);
             sl.nkb = fe ? fe->nkb : 0;
             auto g = group_of_nkb.find(sl.nkb);
             if (g == group_of_nkb.end()) {
@@ -2693,7 +2687,7 @@ static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_d
             if (n == 0) continue;
             Prepared p;
             p.sz = Sizing{};                                       // (the pads are the list's)
-            p.fx = find_fx_entry(8 * (pl.group_nkb[g] - 2));
+            p.fx = find_entry_for_pad<FxEntry>(8 * (pl.group_nkb[g] - 2));
             p.mxt = &table;
             p.mx_quirk = quirk;
             const FwFrame* ft = static_cast<const FwFrame*>(ctx->fs_table) + at;
@@ -3124,7 +3118,7 @@ static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int 
         HIP_TRY(ctx, hipMemset(stamps, 0, 64));
     }
     if (chsel) {
-        const Fw3Entry* fe3 = find_fw3_entry(nkb);
+        const Fw3Entry* fe3 = find_entry<Fw3Entry>(nkb);
         if (!fe3 || vdump || stamps) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for a subset of three channels: no kernel instantiated for this pad");
         TimedLaunch t(ctx, 0, nframes);
         HIP_TRY(ctx, fe3->blur_u8(ctx->stream, d_src, d_dst, p.mxt->frags_row, g, ctx->num_cus, p.mx_quirk ? &qk : nullptr, ctx->fx_strips, chsel, pt, ft));
@@ -4268,7 +4262,7 @@ int blur_gaussian_sigmas_plan(int rows, int cols, int channels, const double* si
         out[3 * c + 1] = out[3 * c + 2] = 0;
         if (g < 0) continue;
         const int pad = pffft_sizing(rows, cols, sg.sigma[g]).pad;
-        const FxEntry* fe = find_fx_entry(pad);
+        const FxEntry* fe = find_entry_for_pad<FxEntry>(pad);
         out[3 * c + 1] = pad;
         out[3 * c + 2] = fe ? fe->nkb : 0;
     }
@@ -4589,7 +4583,7 @@ int blur_mx_fragments(const float* taps, int pad, int nkb, uint16_t* out)
 
 int blur_mx_window_blocks(int pad)
 {
-    const MxEntry* e = pad >= 0 ? find_mx_entry(pad) : nullptr;
+    const MxEntry* e = pad >= 0 ? find_entry_for_pad<MxEntry>(pad) : nullptr;
     return e ? e->nkb : 0;
 }
 

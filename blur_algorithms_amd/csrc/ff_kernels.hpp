@@ -518,10 +518,6 @@ template <typename T> struct FfEntryT {
     hipError_t (*blur)(hipStream_t, const T* src, T* dst, const void* frags, FxGeom g, int ch, int num_cus, const FfQuirk& qk, bool quirk, const T* strips,
                        FwChSel chsel, FwPitch pt, const FwFrame* ft);
 };
-using FfEntry = FfEntryT<float>;
-using FfEntryU16 = FfEntryT<uint16_t>;
-using FfEntryF16 = FfEntryT<ff_f16>;
-using FfEntryBf16 = FfEntryT<ff_bf16>;
 
 template <typename T, int NKB, int CH> hipError_t ff_launch_ch(hipStream_t st, const T* src, T* dst, const void* frags, FxGeom g, int num_cus, const FfQuirk& qk,
                                                                bool quirk, const T* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
@@ -556,42 +552,7 @@ template <typename T, int NKB> hipError_t ff_launch(hipStream_t st, const T* src
     return hipErrorInvalidValue;
 }
 
-#define BLUR_FF(NKB_)                                                                                       \
-    namespace blur_amd {                                                                                    \
-    const FfEntry* ff_entry_##NKB_()                                                                        \
-    {                                                                                                       \
-        static const FfEntry e = { NKB_, ff_launch<float, NKB_> };                                          \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    }
-
-// the u16 instantiations: translation units of their own (ff_u16_conv_<NKB>.hip)
-#define BLUR_FF_U16(NKB_)                                                                                   \
-    namespace blur_amd {                                                                                    \
-    const FfEntryU16* ff_u16_entry_##NKB_()                                                                 \
-    {                                                                                                       \
-        static const FfEntryU16 e = { NKB_, ff_launch<uint16_t, NKB_> };                                    \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    }
-
-// the float16 / bfloat16 instantiations: translation units of their own (ff_f16_conv_<NKB>.hip, ff_bf16_conv_<NKB>.hip)
-#define BLUR_FF_F16(NKB_)                                                                                   \
-    namespace blur_amd {                                                                                    \
-    const FfEntryF16* ff_f16_entry_##NKB_()                                                                 \
-    {                                                                                                       \
-        static const FfEntryF16 e = { NKB_, ff_launch<ff_f16, NKB_> };                                      \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    }
-#define BLUR_FF_BF16(NKB_)                                                                                  \
-    namespace blur_amd {                                                                                    \
-    const FfEntryBf16* ff_bf16_entry_##NKB_()                                                               \
-    {                                                                                                       \
-        static const FfEntryBf16 e = { NKB_, ff_launch<ff_bf16, NKB_> };                                    \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    }
+// ff_conv.hip makes the entries: FfEntryT<T> for every window class and pixel type
 
 // ---- what runs before the fused kernel (engine.hip) ------------------------------------------------------------------
 // strips[f][strip][row][CH (128 + 2 pada)] samples: the window of an edge chunk with the mirrored pixels in place.  A thread moves

@@ -583,7 +583,7 @@ template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* s
     return hipGetLastError();
 }
 
-// the three-channel entry (FxEntry; fx_registry.hpp: find_fx_entry) of the wide windows
+// the three-channel entry (FxEntry; fx_registry.hpp: find_entry_for_pad) of the wide windows
 template <int NKB> hipError_t fw_launch_u8c3(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk,
                                              const uint8_t* strips, float* vdump, unsigned long long* stamps)
 {
@@ -612,7 +612,7 @@ template <int NKB> hipError_t fw_launch_u8c3_sel(hipStream_t st, const uint8_t* 
     return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
 }
 
-// the one- and four-channel entry (FcEntry; fx_registry.hpp: find_fc_entry) of every window class
+// the one- and four-channel entry (FcEntry; fx_registry.hpp: find_entry) of every window class
 template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk,
                                               const uint8_t* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
 {
@@ -621,29 +621,7 @@ template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src
     return hipErrorInvalidValue;
 }
 
-// fw_conv_<NKB>.hip: BLUR_FW(NKB) for every window class (one and four channels, and three for the channel-subset launches),
-// BLUR_FW_C3(NKB) as well for the wide ones (whole BGR frames)
-#define BLUR_FW(NKB_)                                                                                       \
-    namespace blur_amd {                                                                                    \
-    const FcEntry* fc_entry_##NKB_()                                                                        \
-    {                                                                                                       \
-        static const FcEntry e = { NKB_, fw_launch_u8c14<NKB_> };                                           \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    const Fw3Entry* fw3_entry_##NKB_()                                                                      \
-    {                                                                                                       \
-        static const Fw3Entry e = { NKB_, fw_launch_u8c3_sel<NKB_> };                                       \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    }
-#define BLUR_FW_C3(NKB_)                                                                                    \
-    namespace blur_amd {                                                                                    \
-    const FxEntry* fx_entry_##NKB_()                                                                        \
-    {                                                                                                       \
-        static const FxEntry e = { NKB_, fw_launch_u8c3<NKB_> };                                            \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    }
+// fw_conv.hip makes the entries: FcEntry and Fw3Entry for every window class, FxEntry as well for the wide ones (whole BGR frames)
 
 // ---- what runs before the 1- and 4-channel kernels (engine.hip) ------------------------------------------------------
 // strips[f][strip][row][CH (128 + 2 pada)]: the window of an edge chunk with the mirrored pixels in place (fx_edge_strips_body for

@@ -1153,13 +1153,4 @@ template <int NKB> hipError_t fx_launch_u8(hipStream_t st, const uint8_t* src, u
     return hipGetLastError();
 }
 
-#define BLUR_FX(NKB_)                                                                                       \
-    namespace blur_amd {                                                                                    \
-    const FxEntry* fx_entry_##NKB_()                                                                        \
-    {                                                                                                       \
-        static const FxEntry e = { NKB_, fx_launch_u8<NKB_> };                                              \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    }
-
 }  // namespace blur_amd

@@ -1,43 +1,48 @@
-// fx_registry.hpp -- the window classes (NKB blocks of 16 positions) the fused matrix-core kernels are instantiated for, one
-// translation unit per class and kernel file.  A kernel serves every pad <= 8 (NKB - 2).
-//   three channels   fx_kernels.hpp (three channels per workgroup) for NKB <= 11 (fx_conv_<NKB>.hip), fw_kernels.hpp (one channel
-//                    per workgroup) for 13 .. 23 (fw_conv_<NKB>.hip): FxEntry
-//   one, four        fw_kernels.hpp for every class (fw_conv_<NKB>.hip): FcEntry
-//   three, a subset  fw_kernels.hpp for every class (fw_conv_<NKB>.hip): Fw3Entry (one sigma per channel)
-//   float32          ff_kernels.hpp for every class (ff_conv_<NKB>.hip; ff_registry.hpp): FfEntry
+// fx_registry.hpp -- the window classes the fused and the two-kernel matrix-core kernels are instantiated for, and the one table of
+// their entries.  A class is NKB blocks of 16 window positions; its kernels serve every pad <= 8 (NKB - 2):
+//   NKB    3   5   7   9  11  13   15   17   19   21   23
+//   pad    8  24  40  56  72  88  104  120  136  152  168
+// Each family has one instantiation unit, which the Makefile compiles once per class (-DBLUR_INST_NKB) into build/<family>_conv_<NKB>.o:
+//   fx_conv.hip   fx_kernels.hpp, three channels per workgroup, NKB <= 11: FxEntry
+//   fw_conv.hip   fw_kernels.hpp, one channel per workgroup, every class: FcEntry (one and four channels) and Fw3Entry (three channels,
+//                 a subset per launch: one sigma per channel); NKB >= 13 also FxEntry (whole BGR frames, pad 73 .. 168)
+//   ff_conv.hip   ff_kernels.hpp, every class, once per pixel type as well (-DBLUR_INST_T; build/ff_[u16_|f16_|bf16_]conv_<NKB>.o):
+//                 FfEntryT<T> for float, uint16_t, ff_f16 and ff_bf16
+//   mx_conv.hip   mx_kernels.hpp, every class: MxEntry
+// This header names no entry type and needs no kernel header: engine.hip includes ff_kernels.hpp well after it.
 #pragma once
-#include "fw_kernels.hpp"
+#include <array>
+// the only list of the classes in C++ (the Makefile's CLASSES names the objects after it)
 #define BLUR_FX_CLASSES(X) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23)
 namespace blur_amd {
-#define BLUR_FX_DECL(NKB_) const FxEntry* fx_entry_##NKB_(); const FcEntry* fc_entry_##NKB_(); const Fw3Entry* fw3_entry_##NKB_();
-BLUR_FX_CLASSES(BLUR_FX_DECL)
-#undef BLUR_FX_DECL
-inline const FxEntry* find_fx_entry(int pad)
+constexpr bool fx_is_class(int nkb)
 {
-#define BLUR_FX_ITEM(NKB_) fx_entry_##NKB_(),
-    static const FxEntry* const list[] = { BLUR_FX_CLASSES(BLUR_FX_ITEM) };
+#define BLUR_FX_ITEM(NKB_) || nkb == NKB_
+    return false BLUR_FX_CLASSES(BLUR_FX_ITEM);
 #undef BLUR_FX_ITEM
-    for (const FxEntry* e : list)
+}
+// The entry of type E for one class.  Declared only: every <E, NKB> is an explicit specialisation in its family's instantiation unit,
+// so a translation unit that looks entries up (engine.hip) instantiates no kernel.  Every entry type has every class.
+template <class E, int NKB> const E* fx_entry();
+template <class E> const auto& fx_entries()
+{
+#define BLUR_FX_ITEM(NKB_) fx_entry<E, NKB_>(),
+    static const std::array list = { BLUR_FX_CLASSES(BLUR_FX_ITEM) };
+#undef BLUR_FX_ITEM
+    return list;
+}
+// the entry of the class nkb (nullptr: no such class)
+template <class E> const E* find_entry(int nkb)
+{
+    for (const E* e : fx_entries<E>())
+        if (e->nkb == nkb) return e;
+    return nullptr;
+}
+// the entry of the smallest class whose window holds the taps of pad (nullptr: none -- the FFT kernels take over)
+template <class E> const E* find_entry_for_pad(int pad)
+{
+    for (const E* e : fx_entries<E>())
         if (8 * (e->nkb - 2) >= pad) return e;
-    return nullptr;
-}
-inline const FcEntry* find_fc_entry(int nkb)
-{
-#define BLUR_FC_ITEM(NKB_) fc_entry_##NKB_(),
-    static const FcEntry* const list[] = { BLUR_FX_CLASSES(BLUR_FC_ITEM) };
-#undef BLUR_FC_ITEM
-    for (const FcEntry* e : list)
-        if (e->nkb == nkb) return e;
-    return nullptr;
-}
-// three channels, a subset per launch (one sigma per channel): fw_kernels.hpp for every class
-inline const Fw3Entry* find_fw3_entry(int nkb)
-{
-#define BLUR_FW3_ITEM(NKB_) fw3_entry_##NKB_(),
-    static const Fw3Entry* const list[] = { BLUR_FX_CLASSES(BLUR_FW3_ITEM) };
-#undef BLUR_FW3_ITEM
-    for (const Fw3Entry* e : list)
-        if (e->nkb == nkb) return e;
     return nullptr;
 }
 }  // namespace blur_amd

@@ -583,7 +583,7 @@ __global__ __launch_bounds__(256) void mx_quirk_cols(const float* __restrict__ v
 }
 #endif  // BLUR_MX_QUIRK_KERNELS
 
-// ---- launchers: one translation unit per NKB (mx_conv_<NKB>.hip) --------------------------------------------------
+// ---- launchers: one object per NKB (mx_conv.hip -> mx_conv_<NKB>.o) --------------------------------------------------
 struct MxEntry {
     int nkb;          // window blocks: pad <= 8 (nkb - 2)
     hipError_t (*row_u8)(hipStream_t, const uint8_t* src, float* V, const void* frags, MxGeom g, int num_cus, int* spart, float* vpart);
@@ -630,14 +630,5 @@ template <int NKB> hipError_t mx_launch_col_u8(hipStream_t st, const float* V, u
     else hipLaunchKernelGGL((mx_colpass_u8<NKB, false>), grid, dim3(256), 0, st, V, dst, static_cast<const mx_half8*>(frags), g, nstrips, qcol, tps, nseg, qrow);
     return hipGetLastError();
 }
-
-#define BLUR_MX(NKB_)                                                                                       \
-    namespace blur_amd {                                                                                    \
-    const MxEntry* mx_entry_##NKB_()                                                                        \
-    {                                                                                                       \
-        static const MxEntry e = { NKB_, mx_launch_row_u8<NKB_>, mx_launch_col_u8<NKB_> };                  \
-        return &e;                                                                                          \
-    }                                                                                                       \
-    }
 
 }  // namespace blur_amd

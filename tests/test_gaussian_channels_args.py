@@ -114,7 +114,7 @@ def fw_cfg(nkb):
     return pada, win, gpr, per, cs, ips
 
 
-# the kernel's instantiations (fw_conv_<NKB>.hip): 1 and 4 channels for every window class, 3 for the wide ones (NKB >= 13)
+# the kernel's instantiations (fw_conv.hip, one object per window class): 1 and 4 channels for every window class, 3 for the wide ones (NKB >= 13)
 FW_KERNELS = [(ch, nkb) for ch in (1, 3, 4) for nkb in (3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23) if ch != 3 or nkb >= 13]
 
 

@@ -7,8 +7,13 @@
                                                           gained a spill or scratch (exit status 1 then).  STRIP: a regular
                                                           expression for the pieces of the mangled names to leave out when the
                                                           builds are matched (a parameter that one build added: PKNS_7FwFrameE)
+    tools/kernel_resources.py --same-code BASE NEW        whether two builds hold the same device code: per object (directories are
+                                                          matched by basename), the same kernel names and the same sha256 of the
+                                                          code object's .text (not of the whole code object: its metadata names the
+                                                          source file).  Exit status 1 on any difference or unmatched object
 """
 import glob
+import hashlib
 import os
 import re
 import subprocess
@@ -19,14 +24,19 @@ LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 FIELDS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size")
 
 
-def kernels(obj, arch="gfx950"):
-    """{kernel name: (vgpr, agpr, sgpr, vgpr spills, sgpr spills, scratch bytes)} of one host object with an embedded code object"""
+def kernels(obj, arch="gfx950", text=False):
+    """{kernel name: (vgpr, agpr, sgpr, vgpr spills, sgpr spills, scratch bytes)} of one host object with an embedded code object;
+    with text, the sha256 of the code object's .text as well: (kernels, digest)"""
     with tempfile.TemporaryDirectory() as tmp:
         fb, co = os.path.join(tmp, "a.hipfb"), os.path.join(tmp, "a.co")
         subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(tmp, "copy.o")])
         subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--" + arch,
                                "--input=" + fb, "--output=" + co])
         notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
+        if text:
+            subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.text", co, os.path.join(tmp, "a.text")])
+            with open(os.path.join(tmp, "a.text"), "rb") as f:
+                digest = hashlib.sha256(f.read()).hexdigest()
     out = {}
     for block in re.split(r"\n\s*- \.agpr_count:", "\n" + notes)[1:]:
         block = "    - .agpr_count:" + block
@@ -38,14 +48,43 @@ def kernels(obj, arch="gfx950"):
             m = re.search(re.escape(f) + r":\s+(\d+)", block)
             vals.append(int(m.group(1)) if m else 0)
         out[name.group(1)] = tuple(vals)
-    return out
+    return (out, digest) if text else out
 
 
 def objects(path):
     return sorted(glob.glob(os.path.join(path, "*.o"))) if os.path.isdir(path) else [path]
 
 
+def same_code(base, new):
+    """0 if the objects of base and new (two directories, or two objects) hold the same kernels and the same device .text"""
+    if os.path.isdir(base):
+        bo, no = ({os.path.basename(o): o for o in objects(d)} for d in (base, new))
+    else:
+        bo, no = {os.path.basename(new): base}, {os.path.basename(new): new}
+    bad = nobj = nker = 0
+    for name in sorted(set(bo) | set(no)):
+        if name not in bo or name not in no:
+            print("unmatched object", name, "(only in %s)" % (new if name in no else base))
+            bad += 1
+            continue
+        try:
+            (kb, tb), (kn, tn) = kernels(bo[name], text=True), kernels(no[name], text=True)
+        except subprocess.CalledProcessError:
+            continue                                      # no device code in this object
+        nobj += 1
+        nker += len(kn)
+        for k in sorted(set(kb) ^ set(kn)):
+            print("unmatched kernel", name, k)
+        if set(kb) != set(kn) or tb != tn:
+            print("differs", name, ".text", tb[:16], "->", tn[:16])
+            bad += 1
+    print("%d objects with device code compared (%d kernels), %d differ or are unmatched" % (nobj, nker, bad))
+    return 1 if bad else 0
+
+
 def main(argv):
+    if argv and argv[0] == "--same-code":
+        return same_code(argv[1], argv[2])
     if argv and argv[0] == "--diff":
         base, new, strip = argv[1], argv[2], argv[3] if len(argv) > 3 else None
         worse = changed = total = 0
