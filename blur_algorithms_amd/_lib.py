@@ -143,6 +143,14 @@ SYMBOLS = {
         C.POINTER(BlurOpts)]),
     "blur_gaussian_bf16_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
         C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_nv12_batch_dev": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_nv12_dev": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_nv12_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_p016_batch_dev": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_p016_dev": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_p016_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
     "blur_gaussian_sigmas_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "blur_gaussian_u8_frame_sigmas_batch_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
     "blur_gaussian_f32_frame_sigmas_batch_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),

@@ -238,6 +238,76 @@ def _gauss_tensor(image, out, dtype, device=None):
     return t, dst, shape, (sl[0] * es, sl[1] * es, dl[0] * es, dl[1] * es)
 
 
+def _nv12_layout(y_shape, y_strides, uv_shape, uv_strides):
+    """The layout of an NV12 / P016 surface given as two tensors, from their shapes and strides (in elements): y is [rows, cols] or
+    [n, rows, cols], uv is [rows / 2, cols / 2, 2] or [n, rows / 2, cols / 2, 2] (interleaved Cb/Cr pairs).  Returns (n, rows, cols,
+    pitch, y frame stride, uv frame stride) in elements.  Both planes must be row-pitched views with the SAME pitch >= cols: luma
+    strides ([fs_y,] pitch, 1), chroma strides ([fs_uv,] pitch, 2, 1) -- the two planes of one decoder surface, regions of them, or
+    contiguous tensors (pitch = cols).  ValueError for mismatched shapes, odd sizes, unequal pitches and every other view.  (The
+    stride of a dimension of size 1 addresses nothing and is not looked at.)"""
+    y_shape, y_strides, uv_shape, uv_strides = tuple(y_shape), tuple(y_strides), tuple(uv_shape), tuple(uv_strides)
+    if len(y_shape) != len(y_strides) or len(uv_shape) != len(uv_strides) or len(y_shape) not in (2, 3) or len(uv_shape) != len(y_shape) + 1:
+        raise ValueError("expected y [rows, cols] with uv [rows / 2, cols / 2, 2], or y [n, rows, cols] with uv [n, rows / 2, cols / 2, 2]")
+    if len(y_shape) == 3:
+        (n, rows, cols), (fs_y, pitch, sx) = y_shape, y_strides
+        (n_uv, crows, ccols, two), (fs_uv, cpitch, cx, cc) = uv_shape, uv_strides
+    else:
+        n = n_uv = 1
+        fs_y = fs_uv = None
+        (rows, cols), (pitch, sx) = y_shape, y_strides
+        (crows, ccols, two), (cpitch, cx, cc) = uv_shape, uv_strides
+    if rows <= 0 or cols <= 0 or rows % 2 or cols % 2:
+        raise ValueError("rows and cols of the luma plane must be positive and even, got %d x %d" % (rows, cols))
+    if (n_uv, crows, ccols, two) != (n, rows // 2, cols // 2, 2):
+        raise ValueError("uv must be %s for y %s" % ((([n] if len(y_shape) == 3 else []) + [rows // 2, cols // 2, 2]), list(y_shape)))
+    if sx != 1 or cc != 1 or (ccols > 1 and cx != 2):
+        raise ValueError("y and uv must be row-pitched views: samples of a row (Cb/Cr pairs of a chroma row) next to each other")
+    if pitch < cols:
+        raise ValueError("the rows of y overlap or run backwards (pitch %d < cols %d)" % (pitch, cols))
+    if crows > 1 and cpitch != pitch:
+        raise ValueError("y and uv must have the same row pitch (got %d and %d elements)" % (pitch, cpitch))
+    if n > 1:
+        if fs_y < (rows - 1) * pitch + cols or fs_uv < (crows - 1) * pitch + cols:
+            raise ValueError("the frames of y or of uv overlap or run backwards")
+    else:
+        fs_y, fs_uv = rows * pitch, crows * pitch
+    return n, rows, cols, pitch, fs_y, fs_uv
+
+
+def _nv12_sigmas(sigma):
+    """the three sigmas (Y, Cb, Cr) of an NV12 / P016 call, each in pixels of its own plane: a scalar s means (s, s / 2, s / 2), the
+    same blur in luma pixels on all three; a sequence of three is taken as given"""
+    if not _is_sigma_sequence(sigma):
+        s = float(sigma)
+        return (s, s / 2, s / 2)
+    vals = tuple(float(v) for v in sigma)
+    if len(vals) != 3:
+        raise ValueError("sigma: expected a number or a sequence of 3 (Y, Cb, Cr), got %d" % len(vals))
+    return vals
+
+
+def _nv12_tensors(y, uv, out, require_cuda=True):
+    """the checks of BlurContext.gaussian_nv12 on its tensors, before the library is called: (y, uv, y_out, uv_out, source layout,
+    result layout), the layouts as _nv12_layout returns them.  uint8 is NV12, uint16 P016"""
+    import torch
+    for t in (y, uv):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.uint16) or (require_cuda and not t.is_cuda):
+            raise ValueError("expected CUDA uint8 (NV12) or uint16 (P016) tensors y and uv")
+    if y.dtype != uv.dtype or y.device != uv.device:
+        raise ValueError("y and uv must have the same dtype and device")
+    sl = _nv12_layout(y.shape, y.stride(), uv.shape, uv.stride())
+    if out is None:
+        return y, uv, y, uv, sl, sl
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise ValueError("out: expected (y_out, uv_out)")
+    yo, uvo = out
+    for t, s in ((yo, y), (uvo, uv)):
+        if not isinstance(t, torch.Tensor) or t.dtype != s.dtype or t.device != s.device or tuple(t.shape) != tuple(s.shape):
+            raise ValueError("out must match the input: (y_out, uv_out) with the shapes, dtype and device of (y, uv)")
+    dl = _nv12_layout(yo.shape, yo.stride(), uvo.shape, uvo.stride())
+    return y, uv, yo, uvo, sl, dl
+
+
 def _is_sigma_sequence(sigma):
     """whether `sigma` is one value per channel (a list, tuple, numpy array or tensor of numbers) rather than a scalar.  A 0-d
     numpy array or tensor is a scalar, as it was before sequences were accepted"""
@@ -681,6 +751,50 @@ class BlurContext:
         torch.bfloat16 tensor: host round trip, returns a new CPU tensor (numpy has no bfloat16; a numpy array is refused).
         """
         return self._gaussian(image, sigma, out, nyquist_quirk, engine, BF16, "bf16")
+
+    def gaussian_nv12(self, y, uv, sigma, out=None, nyquist_quirk=True, engine=None):
+        """Gaussian blur of a decoded video surface where it lies: NV12 (uint8) or P010 / P016 (uint16).  y is the luma plane [rows,
+        cols] or [n, rows, cols]; uv the plane of interleaved Cb/Cr pairs [rows / 2, cols / 2, 2] or [n, rows / 2, cols / 2, 2]; both
+        row-pitched views with the same pitch (the two planes of one surface: `surf[:rows, :cols]` and `surf[h:h + rows // 2,
+        :cols].view(rows // 2, cols // 2, 2)`), or contiguous tensors.  The strides supply the pitch and the two frame strides.
+        sigma: a number s blurs all three planes alike in luma pixels -- (s, s / 2, s / 2), each sigma being in pixels of its own
+        plane; a sequence (Y, Cb, Cr) is taken as given, and 0 leaves that plane or channel as it is (`(0, 5, 5)`: the chroma
+        smoothing of a YCrCb image).  Each plane is, bit for bit, what gaussian() / gaussian_u16() returns for it as a one-channel
+        image (blur_gaussian_nv12_batch_dev, blur_gaussian_p016_batch_dev).  P016 results keep all 16 bits: the low bits of P010
+        data are not masked.  engine: None (the library's choice), "fused" or "fft", per plane.
+
+        torch CUDA tensors: asynchronous on torch's current stream; out=(y_out, uv_out) or, by default, in place; returns (y_out,
+        uv_out).  numpy arrays (contiguous): host round trip, returns new arrays (or `out`).  ValueError, before the library is
+        called: mismatched shapes or dtypes, odd sizes, unequal row pitches of y and uv, anything that is not a row-pitched view.
+        """
+        sg = (C.c_double * 3)(*_nv12_sigmas(sigma))
+        o = self._opts(nyquist_quirk, engine=engine)
+        if isinstance(y, np.ndarray) or isinstance(uv, np.ndarray):
+            if not (isinstance(y, np.ndarray) and isinstance(uv, np.ndarray)) or y.dtype != uv.dtype or y.dtype not in (np.uint8, np.uint16):
+                raise ValueError("expected uint8 (NV12) or uint16 (P016) arrays y and uv")
+            ya, uva = np.ascontiguousarray(y), np.ascontiguousarray(uv)
+            n, rows, cols, _, _, _ = _nv12_layout(ya.shape, [s // ya.itemsize for s in ya.strides], uva.shape, [s // uva.itemsize for s in uva.strides])
+            yo, uvo = (np.empty_like(ya), np.empty_like(uva)) if out is None else out
+            for t, s in ((yo, ya), (uvo, uva)):
+                if not isinstance(t, np.ndarray) or t.shape != s.shape or t.dtype != s.dtype or not t.flags["C_CONTIGUOUS"]:
+                    raise ValueError("out must match the input: contiguous (y_out, uv_out)")
+            host_entry = self._lib.blur_gaussian_nv12_host if ya.dtype == np.uint8 else self._lib.blur_gaussian_p016_host
+            ny = rows * cols
+            for f in range(n):
+                src = np.concatenate([ya.reshape(n, -1)[f], uva.reshape(n, -1)[f]])
+                res = np.empty_like(src)
+                self._check(host_entry(self._h, src.ctypes.data, res.ctypes.data, rows, cols, sg, C.byref(o)))
+                yo.reshape(n, -1)[f] = res[:ny]
+                uvo.reshape(n, -1)[f] = res[ny:]
+            return yo, uvo
+        y, uv, yo, uvo, sl, dl = _nv12_tensors(y, uv, out)
+        n, rows, cols = sl[:3]
+        es = y.element_size()
+        self.use_torch_stream()
+        entry = self._lib.blur_gaussian_nv12_batch_dev if es == 1 else self._lib.blur_gaussian_p016_batch_dev
+        self._check(entry(self._h, y.data_ptr(), uv.data_ptr(), sl[3] * es, sl[4] * es, sl[5] * es, yo.data_ptr(), uvo.data_ptr(), dl[3] * es, dl[4] * es, dl[5] * es,
+                          n, rows, cols, sg, C.byref(o)))
+        return yo, uvo
 
     def gaussian_per_frame(self, frames, sigmas, out=None, nyquist_quirk=True, engine=None):
         """Gaussian blur of uint8 frames [n, rows, cols, C] or [n, rows, cols] (C in {1, 3, 4}) with one sigma per FRAME: `sigmas` is a

@@ -1792,7 +1792,7 @@ static FwPitch fw_pitch_of(const ChLayout& L)
 static int run_fx_u8c3(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nframes, int rows, int cols, const Prepared& p, float* vdump, FwChSel chsel,
                        const ChLayout* lay, const FwFrame* ft = nullptr);
 
-// the fused kernel for CH = 1, 4 (fw_kernels.hpp): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
+// the fused kernel for CH = 1, 2, 4 (fw_kernels.hpp; 2: the chroma plane of an NV12 surface, blur_nv_batch_impl): the pre-pass (the quirk's sums, the edge chunks' strips), then the kernel.
 // Frames are disjoint from the destination here (blur_ch_batch_impl copies overlapping ones first).
 // chsel: the channels to blur (blur_ch_sigmas_batch_impl: one sigma per channel); the pre-pass reads every channel (a pixel is one
 // dword) and completes the quirk's row sums of these channels only
@@ -1841,9 +1841,11 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
         int* cpart = const_cast<int*>(qk.cpart);
         long long* zsum = const_cast<long long*>(qk.zsum);
         auto kern = ch == 1 ? (G == 1 ? fc_prepass<1, 1> : (G == 2 ? fc_prepass<1, 2> : fc_prepass<1, 4>))
+                  : ch == 2 ? (G == 1 ? fc_prepass<2, 1> : (G == 2 ? fc_prepass<2, 2> : fc_prepass<2, 4>))
                             : (G == 1 ? fc_prepass<4, 1> : (G == 2 ? fc_prepass<4, 2> : fc_prepass<4, 4>));
         auto kern_frames = ch == 1 ? (G == 1 ? fc_prepass_frames<1, 1> : (G == 2 ? fc_prepass_frames<1, 2> : fc_prepass_frames<1, 4>))
                                    : (G == 1 ? fc_prepass_frames<4, 1> : (G == 2 ? fc_prepass_frames<4, 2> : fc_prepass_frames<4, 4>));
+        if (ft && ch == 2) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for 2 channels: no launch over frames with their own sigmas");
         if (ft)
             hipLaunchKernelGGL(kern_frames, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, pada, nbands, nbatches,
                                cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel), pt.src_pitch, pt.src_frame, ft);
@@ -1920,6 +1922,14 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
         auto kern_frames = ch == 1 ? pick(ff_prepass_frames<T, 1, 1>, ff_prepass_frames<T, 1, 2>, ff_prepass_frames<T, 1, 4>)
                                    : (ch == 3 ? pick(ff_prepass_frames<T, 3, 1>, ff_prepass_frames<T, 3, 2>, ff_prepass_frames<T, 3, 4>)
                                               : pick(ff_prepass_frames<T, 4, 1>, ff_prepass_frames<T, 4, 2>, ff_prepass_frames<T, 4, 4>));
+        auto fin = ch == 1 ? ff_finalize<1> : (ch == 3 ? ff_finalize<3> : ff_finalize<4>);
+        if constexpr (u16) {                  // two channels (the chroma plane of a P016 surface, blur_nv_batch_impl): u16 only, no frame lists
+            if (ch == 2) {
+                if (ft) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for 2 channels: no launch over frames with their own sigmas");
+                kern = pick(ff_prepass<T, 2, 1>, ff_prepass<T, 2, 2>, ff_prepass<T, 2, 4>);
+                fin = ff_finalize<2>;
+            }
+        }
         if (n_alt + n_strip > 0 && ft)
             hipLaunchKernelGGL(kern_frames, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, mbits, spart, cpart, strips, rows, cols, pada, nbands, nbatches, ne,
                                n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0, pt.src_pitch, pt.src_frame, ft);
@@ -1928,7 +1938,6 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
                                nbatches, ne, n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0, pt.src_pitch, pt.src_frame);
         HIP_TRY(ctx, hipGetLastError());
         if (quirk) {
-            auto fin = ch == 1 ? ff_finalize<1> : (ch == 3 ? ff_finalize<3> : ff_finalize<4>);
             auto fin_frames = ch == 1 ? ff_finalize_frames<1> : (ch == 3 ? ff_finalize_frames<3> : ff_finalize_frames<4>);
             if (ft) hipLaunchKernelGGL(fin_frames, dim3(nframes), dim3(256), 0, ctx->stream, spart, srow, zsum, rows, nbatches, ft);
             else hipLaunchKernelGGL(fin, dim3(nframes), dim3(256), 0, ctx->stream, spart, srow, zsum, rows, p.sz.pad, nbatches);
@@ -2080,9 +2089,10 @@ static int check_ch_args(blur_ctx* ctx, const void* src, const void* dst, int nf
 // the arguments a pitched entry adds (blur_gaussian_*_pitched_batch_dev), without the device: pitches and frame strides in bytes
 // src_broadcast: a source frame stride of 0 is accepted for any nframes (the one-sigma-per-frame entries: every frame of the result
 // is blurred from the same source frame)
-static int check_ch_layout(blur_ctx* ctx, int nframes, int rows, int cols, int channels, size_t es, const ChLayout& L, bool src_broadcast = false)
+// two_ok: two channels are legal (the chroma plane of an NV12 / P016 surface: blur_nv_batch_impl only)
+static int check_ch_layout(blur_ctx* ctx, int nframes, int rows, int cols, int channels, size_t es, const ChLayout& L, bool src_broadcast = false, bool two_ok = false)
 {
-    if (rows <= 0 || cols <= 0 || (channels != 1 && channels != 3 && channels != 4)) return BLUR_OK;       // (refused by the other checks)
+    if (rows <= 0 || cols <= 0 || (channels != 1 && channels != 3 && channels != 4 && !(two_ok && channels == 2))) return BLUR_OK;       // (refused by the other checks)
     const size_t rowbytes = static_cast<size_t>(cols) * channels * es;
     if (L.spitch < rowbytes || L.dpitch < rowbytes) return fail(ctx, BLUR_ERR_INVALID, "row pitch below cols * channels * sizeof(element)");
     if (L.spitch % es || L.dpitch % es || L.sframe % es || L.dframe % es)
@@ -2281,10 +2291,12 @@ struct SigmaGroups {
 
 // The arguments of every blur_gaussian_*_sigmas_* entry, without a context or a device: the status and, where it is not BLUR_OK,
 // its text in *why.  Every entry of sigmas is checked here, before anything is launched: a refused call has written nothing.
-static int ch_sigmas_status(const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, SigmaGroups& sg, const char** why)
+// two_ok: two channels are legal (the chroma plane of an NV12 / P016 surface: blur_nv_batch_impl only)
+static int ch_sigmas_status(const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, SigmaGroups& sg, const char** why,
+                            bool two_ok = false)
 {
     auto no = [&](int rc, const char* text) { *why = text; return rc; };
-    if (channels != 1 && channels != 3 && channels != 4) return no(BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
+    if (channels != 1 && channels != 3 && channels != 4 && !(two_ok && channels == 2)) return no(BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
     if (!src || !dst || nframes < 0) return no(BLUR_ERR_INVALID, "null frame pointer or negative frame count");
     if (rows <= 0 || cols <= 0) return no(BLUR_ERR_INVALID, "rows and cols must be positive");
     if (!sigmas) return no(BLUR_ERR_INVALID, "sigmas must point to one sigma per channel");
@@ -2308,10 +2320,11 @@ static int ch_sigmas_status(const void* src, const void* dst, int nframes, int r
 }
 
 // the same for an entry with a context: the arguments' status first (ctx = NULL: the status is the same), then the missing context
-static int check_ch_sigmas_args(blur_ctx* ctx, const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, SigmaGroups& sg)
+static int check_ch_sigmas_args(blur_ctx* ctx, const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, SigmaGroups& sg,
+                                bool two_ok = false)
 {
     const char* why = nullptr;
-    if (int rc = ch_sigmas_status(src, dst, nframes, rows, cols, channels, sigmas, sg, &why)) return fail(ctx, rc, why);
+    if (int rc = ch_sigmas_status(src, dst, nframes, rows, cols, channels, sigmas, sg, &why, two_ok)) return fail(ctx, rc, why);
     return ctx ? BLUR_OK : BLUR_ERR_INVALID;
 }
 
@@ -2367,7 +2380,7 @@ static int launch_chan_copy(blur_ctx* ctx, const T* src, T* dst, size_t nelem, i
     const int vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 ? 1 : 0;
     const size_t items = vec ? nbytes / 16 + 256 : nelem;
     const unsigned blocks = static_cast<unsigned>(std::min<size_t>((items + 255) / 256, 16384));
-    auto kern = ch == 3 ? chan_copy<ES, 3> : chan_copy<ES, 4>;
+    auto kern = ch == 3 ? chan_copy<ES, 3> : (ch == 2 ? chan_copy<ES, 2> : chan_copy<ES, 4>);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nbytes, mask, vec);
     HIP_TRY(ctx, hipGetLastError());
     return BLUR_OK;
@@ -2380,16 +2393,18 @@ static int launch_chan_copy(blur_ctx* ctx, const T* src, T* dst, size_t nelem, i
 // the sigma = 0 channels (out of place only), and per group the whole pre-pass (the quirk's sums are weighted by the pad's parity and
 // the strips are as wide as the pad: both belong to the group) and the fused launch over the group's channels, or the plane path
 // over them.  The strips and sums workspaces are reused from group to group.
+// two_ok (blur_nv_batch_impl: the interleaved Cb/Cr plane of an NV12 / P016 surface): channels = 2 is legal, u8 and u16 only.
 template <typename T>
 static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts,
-                                     const ChLayout* lay = nullptr)
+                                     const ChLayout* lay = nullptr, bool two_ok = false)
 {
     constexpr bool u8 = std::is_same_v<T, uint8_t>;
     SigmaGroups sg;
     if (lay)
-        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay)) return rc;
-    if (int rc = check_ch_sigmas_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, sg)) return rc;
-    if (sg.ngroups == 1 && !sg.zero_mask) return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[0], opts, lay);
+        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay, false, two_ok)) return rc;
+    if (int rc = check_ch_sigmas_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, sg, two_ok)) return rc;
+    // (two channels have no scalar entry: one group over both is a launch of this driver)
+    if (sg.ngroups == 1 && !sg.zero_mask && channels != 2) return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[0], opts, lay);
     ChLayout L = lay ? *lay : ch_packed(rows, cols, channels, sizeof(T));
     if (nframes == 1) L.sframe = L.dframe = 0;
     const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
@@ -2413,7 +2428,7 @@ static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, in
                 for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
                     const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
                     T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * L.dframe);
-                    if (int rc = blur_ch_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas, opts, lay)) return rc;
+                    if (int rc = blur_ch_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas, opts, lay, two_ok)) return rc;
                 }
                 return BLUR_OK;
             }
@@ -2466,6 +2481,110 @@ static int blur_ch_sigmas_host(blur_ctx* ctx, const T* src, T* dst, int rows, in
     int rc = BLUR_OK;
     hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) rc = blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const T*>(d), reinterpret_cast<T*>(d + half), 1, rows, cols, channels, sigmas, opts);
+    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
+    return rc;
+}
+
+// ======================================================================================
+// Decoded video surfaces (blur_gaussian_nv12_*, blur_gaussian_p016_*): a rows x cols luma plane and a rows / 2 x cols / 2 plane of
+// interleaved Cb/Cr pairs with the luma's row pitch.  A call is a luma part (one channel, sigmas[0]) and a chroma part (two
+// channels, sigmas[1] and sigmas[2]) of blur_ch_sigmas_batch_impl, on the context's stream: grouping by sigma, launches over a
+// subset of the channels, the copy of overlapping spans and the plane fallback are that driver's.  Two channels are legal there
+// for these calls only (two_ok).
+// ======================================================================================
+struct NvSurface {
+    const void* sy;
+    const void* suv;
+    void* dy;
+    void* duv;
+    size_t spitch, sy_frame, suv_frame, dpitch, dy_frame, duv_frame;
+};
+
+// The arguments of every blur_gaussian_{nv12,p016}_* entry, without a context or a device (es: bytes per sample): the status and,
+// where it is not BLUR_OK, its text in *why.  Layout errors come before BLUR_ERR_UNSUPPORTED.
+static int nv_status(const NvSurface& s, size_t es, int nframes, int rows, int cols, const double* sigmas, const char** why)
+{
+    auto no = [&](int rc, const char* text) { *why = text; return rc; };
+    if (!s.sy || !s.suv || !s.dy || !s.duv || !sigmas || nframes < 0) return no(BLUR_ERR_INVALID, "null plane or sigmas pointer, or negative frame count");
+    if (rows <= 0 || cols <= 0 || (rows & 1) || (cols & 1)) return no(BLUR_ERR_INVALID, "rows and cols must be positive and even (4:2:0 chroma)");
+    const size_t rowbytes = static_cast<size_t>(cols) * es;            // of a luma row and of a chroma row (cols / 2 pairs)
+    if (s.spitch < rowbytes || s.dpitch < rowbytes) return no(BLUR_ERR_INVALID, "row pitch below cols * sizeof(sample)");
+    if (s.spitch % es || s.dpitch % es) return no(BLUR_ERR_INVALID, "row pitch must be a multiple of the sample size");
+    if (nframes > 1) {
+        if (s.sy_frame % es || s.suv_frame % es || s.dy_frame % es || s.duv_frame % es) return no(BLUR_ERR_INVALID, "frame strides must be multiples of the sample size");
+        if (s.sy_frame < ch_frame_span(rows, s.spitch, rowbytes) || s.dy_frame < ch_frame_span(rows, s.dpitch, rowbytes) ||
+            s.suv_frame < ch_frame_span(rows / 2, s.spitch, rowbytes) || s.duv_frame < ch_frame_span(rows / 2, s.dpitch, rowbytes))
+            return no(BLUR_ERR_INVALID, "frame stride below its plane's span: the planes of the batch would overlap");
+    }
+    for (int p = 0; p < 3; ++p)
+        if (!(sigmas[p] >= 0) || !std::isfinite(sigmas[p])) return no(BLUR_ERR_INVALID, "every sigma must be finite and positive, or 0 for a plane that is left as it is");
+    for (int p = 0; p < 3; ++p) {
+        if (sigmas[p] == 0) continue;
+        const int r = p ? rows / 2 : rows, c = p ? cols / 2 : cols;
+        const Sizing sz = pffft_sizing(r, c, sigmas[p]);
+        if (sz.pad > r - 1 || sz.pad > c - 1)
+            return no(BLUR_ERR_UNSUPPORTED, p ? "chroma pad > min(rows / 2, cols / 2) - 1: reflect-101 would read outside the plane (sigmas[1], sigmas[2] are in chroma pixels)"
+                                              : "luma pad > min(rows, cols) - 1: reflect-101 would read outside the plane");
+    }
+    return BLUR_OK;
+}
+
+template <typename T>
+static int blur_nv_batch_impl(blur_ctx* ctx, NvSurface s, int nframes, int rows, int cols, const double* sigmas, const blur_opts* opts)
+{
+    const char* why = nullptr;
+    if (int rc = nv_status(s, sizeof(T), nframes, rows, cols, sigmas, &why)) return fail(ctx, rc, why);
+    if (!ctx) return BLUR_ERR_INVALID;
+    if (nframes <= 1) s.sy_frame = s.suv_frame = s.dy_frame = s.duv_frame = 0;           // (a single frame's strides address nothing)
+    const ChLayout Ly{ s.spitch, s.sy_frame, s.dpitch, s.dy_frame }, Luv{ s.spitch, s.suv_frame, s.dpitch, s.duv_frame };
+    const int crows = rows / 2, ccols = cols / 2;
+    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
+    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, "NV12 / P016 surfaces: engine must be AUTO, FUSED or FFT");
+    if (choice == BLUR_ENGINE_FUSED) {          // every plane's engine before the first launch: a refused call has written nothing
+        for (int p = 0; p < 3; ++p) {
+            if (sigmas[p] == 0 || (p == 2 && sigmas[2] == sigmas[1])) continue;
+            Prepared pr;
+            std::string note;
+            if (int rc = choose_ch_engine<T>(ctx, p ? crows : rows, p ? ccols : cols, p ? 2 : 1, sigmas[p], opts, choice, pr, note, p ? Luv : Ly)) return rc;
+        }
+    }
+    if (nframes == 0) return BLUR_OK;
+    std::string note;
+    const bool blur_y = sigmas[0] > 0, blur_c = sigmas[1] > 0 || sigmas[2] > 0;
+    ctx->engine_note.clear();
+    if (int rc = blur_ch_sigmas_batch_impl<T>(ctx, static_cast<const T*>(s.sy), static_cast<T*>(s.dy), nframes, rows, cols, 1, sigmas, opts, &Ly)) return rc;
+    if (blur_y && ctx->last_family != 6) note = "luma on the plane path: " + ctx->engine_note;
+    ctx->engine_note.clear();
+    if (int rc = blur_ch_sigmas_batch_impl<T>(ctx, static_cast<const T*>(s.suv), static_cast<T*>(s.duv), nframes, crows, ccols, 2, sigmas + 1, opts, &Luv, true)) return rc;
+    if (blur_c && ctx->last_family != 6) note += (note.empty() ? "" : "; ") + std::string("chroma: ") + ctx->engine_note;
+    // family 6: every blurred plane ran on the fused kernel; 0: one took the plane path, and the note names it
+    ctx->last_family = note.empty() ? 6 : 0;
+    ctx->engine_note = note;
+    return BLUR_OK;
+}
+
+// blur_gaussian_{nv12,p016}_host: one packed surface (rows x cols luma samples, then rows / 2 rows of cols chroma samples) through the
+// context's host staging buffer
+template <typename T>
+static int blur_nv_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols, const double* sigmas, const blur_opts* opts)
+{
+    const size_t pitch = cols > 0 ? static_cast<size_t>(cols) * sizeof(T) : 0, ybytes = rows > 0 ? pitch * rows : 0;
+    NvSurface s{ src, reinterpret_cast<const char*>(src) + ybytes, dst, reinterpret_cast<char*>(dst) + ybytes, pitch, 0, 0, pitch, 0, 0 };
+    if (!src || !dst) s.suv = s.duv = nullptr;
+    const char* why = nullptr;
+    if (int rc = nv_status(s, sizeof(T), 1, rows, cols, sigmas, &why)) return fail(ctx, rc, why);
+    if (!ctx) return BLUR_ERR_INVALID;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = ybytes + ybytes / 2, half = (bytes + 255) & ~static_cast<size_t>(255);
+    void* dv = nullptr;
+    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;
+    char* d = static_cast<char*>(dv);
+    int rc = BLUR_OK;
+    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) rc = blur_nv_batch_impl<T>(ctx, NvSurface{ d, d + ybytes, d + half, d + half + ybytes, pitch, 0, 0, pitch, 0, 0 }, 1, rows, cols, sigmas, opts);
     if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
@@ -4338,6 +4457,45 @@ int blur_gaussian_bf16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d
 {
     const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
     return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+// decoded video surfaces (blur_amd.h: blur_gaussian_nv12_*, blur_gaussian_p016_*): pitches and frame strides in bytes
+int blur_gaussian_nv12_batch_dev(blur_ctx* ctx, const uint8_t* d_src_y, const uint8_t* d_src_uv, size_t src_pitch, size_t src_y_frame_stride, size_t src_uv_frame_stride,
+                                 uint8_t* d_dst_y, uint8_t* d_dst_uv, size_t dst_pitch, size_t dst_y_frame_stride, size_t dst_uv_frame_stride, int nframes, int rows,
+                                 int cols, const double* sigmas, const blur_opts* opts)
+{
+    return blur_nv_batch_impl<uint8_t>(ctx, NvSurface{ d_src_y, d_src_uv, d_dst_y, d_dst_uv, src_pitch, src_y_frame_stride, src_uv_frame_stride, dst_pitch,
+                                                       dst_y_frame_stride, dst_uv_frame_stride }, nframes, rows, cols, sigmas, opts);
+}
+
+int blur_gaussian_nv12_dev(blur_ctx* ctx, const uint8_t* d_src_y, const uint8_t* d_src_uv, size_t src_pitch, uint8_t* d_dst_y, uint8_t* d_dst_uv, size_t dst_pitch, int rows,
+                           int cols, const double* sigmas, const blur_opts* opts)
+{
+    return blur_nv_batch_impl<uint8_t>(ctx, NvSurface{ d_src_y, d_src_uv, d_dst_y, d_dst_uv, src_pitch, 0, 0, dst_pitch, 0, 0 }, 1, rows, cols, sigmas, opts);
+}
+
+int blur_gaussian_nv12_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, const double* sigmas, const blur_opts* opts)
+{
+    return blur_nv_host(ctx, src, dst, rows, cols, sigmas, opts);
+}
+
+int blur_gaussian_p016_batch_dev(blur_ctx* ctx, const uint16_t* d_src_y, const uint16_t* d_src_uv, size_t src_pitch, size_t src_y_frame_stride, size_t src_uv_frame_stride,
+                                 uint16_t* d_dst_y, uint16_t* d_dst_uv, size_t dst_pitch, size_t dst_y_frame_stride, size_t dst_uv_frame_stride, int nframes, int rows,
+                                 int cols, const double* sigmas, const blur_opts* opts)
+{
+    return blur_nv_batch_impl<uint16_t>(ctx, NvSurface{ d_src_y, d_src_uv, d_dst_y, d_dst_uv, src_pitch, src_y_frame_stride, src_uv_frame_stride, dst_pitch,
+                                                        dst_y_frame_stride, dst_uv_frame_stride }, nframes, rows, cols, sigmas, opts);
+}
+
+int blur_gaussian_p016_dev(blur_ctx* ctx, const uint16_t* d_src_y, const uint16_t* d_src_uv, size_t src_pitch, uint16_t* d_dst_y, uint16_t* d_dst_uv, size_t dst_pitch,
+                           int rows, int cols, const double* sigmas, const blur_opts* opts)
+{
+    return blur_nv_batch_impl<uint16_t>(ctx, NvSurface{ d_src_y, d_src_uv, d_dst_y, d_dst_uv, src_pitch, 0, 0, dst_pitch, 0, 0 }, 1, rows, cols, sigmas, opts);
+}
+
+int blur_gaussian_p016_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, const double* sigmas, const blur_opts* opts)
+{
+    return blur_nv_host(ctx, src, dst, rows, cols, sigmas, opts);
 }
 
 // one sigma per frame (blur_amd.h)

@@ -24,7 +24,7 @@
 //   * staging: a u16 sample splits EXACTLY into hi + lo (16 bits into 11 + 5), so the dropped x_lo t_lo is the row pass's only
 //     truncation, as for floats;
 //   * loads: CH = 1 one 8-byte load per group of 4 pixels (two registers per group where the float kernel holds four); CH = 3 / 4
-//     the channel's four strided 16-bit loads.  Loads from the image stay inside a row (the edge chunks read strips), so none
+//     the channel's four strided 16-bit loads, and so CH = 2, which u16 alone has (the Cb/Cr plane of a P016 surface).  Loads from the image stay inside a row (the edge chunks read strips), so none
 //     leaves the buffer resource whatever the row's byte count;
 //   * emission: (uint16_t)((uint32_t)(int32_t)(v + 0.5f) & 0xffff) of the float result v: add 0.5, truncate, keep the low 16 bits, no
 //     clamping (chan_pack<uint8_t>'s rule, 16 bits wide), one 16-bit store per lane and output row at stride CH.  (CH = 1: dword
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256, 1) void ff_blur(const T* __restrict__ src, T* 
                                                   int chunks, int tps, int nseg, int ntasks, FfQuirk qk, const T* __restrict__ strips, FwChSel chsel, FwPitch pt,
                                                   const FwFrame* __restrict__ ft)
 {
-    static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
+    static_assert(CH == 1 || CH == 3 || CH == 4 || (CH == 2 && std::is_same_v<T, uint16_t>), "one, three or four channels; u16 also two (the chroma plane of a P016 surface)");
     static_assert(ff_is_pixel_v<T>, "float32, u16, float16 or bfloat16 pixels");
     constexpr bool U16 = std::is_same_v<T, uint16_t>, HALF = ff_is_half_v<T>, W16 = U16 || HALF;      // W16: 16-bit storage
     constexpr uint32_t ES = sizeof(T);                              // bytes per sample
@@ -548,6 +548,10 @@ template <typename T, int NKB> hipError_t ff_launch(hipStream_t st, const T* src
     if constexpr (ff_class_ok_t<T>(NKB, 3)) {
         if (ch == 3) return ff_launch_ch<T, NKB, 3>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt, ft);
         if (ch == 4) return ff_launch_ch<T, NKB, 4>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt, ft);
+    }
+    // two channels: u16 only (the interleaved Cb/Cr plane of a P016 surface, blur_gaussian_p016_*: no public entry takes channels = 2)
+    if constexpr (std::is_same_v<T, uint16_t>) {
+        if (ch == 2) return ff_launch_ch<T, NKB, 2>(st, src, dst, frags, g, num_cus, qk, quirk, strips, chsel, pt, ft);
     }
     return hipErrorInvalidValue;
 }

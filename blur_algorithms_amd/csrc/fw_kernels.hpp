@@ -1,6 +1,6 @@
-// fw_kernels.hpp -- the fused matrix-core kernel that gives a workgroup ONE channel of its strip: u8 images of CH = 1, 3 or 4
-// channels (grayscale, BGR, BGRA / RGBA), every window class (NKB = 3 .. 23 blocks of 16 positions: pad <= 168).  Whole BGR frames
-// with one sigma take CH = 3 for the WIDE windows only (NKB = 13 .. 23: pad 73 .. 168; narrower BGR windows run on fx_blur_u8); the
+// fw_kernels.hpp -- the fused matrix-core kernel that gives a workgroup ONE channel of its strip: u8 images of CH = 1, 2, 3 or 4
+// channels (grayscale, the interleaved Cb/Cr plane of an NV12 surface, BGR, BGRA / RGBA), every window class (NKB = 3 .. 23 blocks
+// of 16 positions: pad <= 168).  Whole BGR frames with one sigma take CH = 3 for the WIDE windows only (NKB = 13 .. 23: pad 73 .. 168; narrower BGR windows run on fx_blur_u8); the
 // narrow CH = 3 instantiations serve the launches over a subset of the channels (one sigma per channel: FwChSel, Fw3Entry).
 //
 // fx_kernels.hpp keeps (NKB - 1) / 2 column-pass accumulator tiles per channel and a wave carries all three channels: 240 AGPRs at
@@ -16,11 +16,12 @@
 //     instruction.
 // What the channel count CH selects, at compile time:
 //   * staging: a group of 4 pixels is 4 CH bytes: one dword (CH = 1: the bytes are the four values), three dwords (CH = 3: two
-//     v_perm_b32 with run-time selectors, the channel is the task's) or one dwordx4 (CH = 4: byte c of each dword);
+//     v_perm_b32 with run-time selectors, the channel is the task's), one dwordx4 (CH = 4: byte c of each dword) or one dwordx2
+//     (CH = 2: bytes c and 2 + c of each dword);
 //   * the quirk's sums: CH = 3 reads fx_prepass's (struct FxQuirk: Srow in parts per batch, the column term by
-//     fx_quirk_cols_tile), CH = 1 and 4 those of fc_prepass below (struct FcQuirk: Srow complete, fc_quirk_cols_tile);
+//     fx_quirk_cols_tile), CH = 1, 2 and 4 those of fc_prepass below (struct FcQuirk: Srow complete, fc_quirk_cols_tile);
 //   * stores: CH = 1 transposes a finished tile's bytes inside lane quads (fx_quad_transpose) so that a lane owns 4 adjacent pixels
-//     of one row: one dword store per lane and row group.  CH = 3 and 4 store single bytes: the output bytes of one channel are
+//     of one row: one dword store per lane and row group.  CH = 2, 3 and 4 store single bytes: the output bytes of one channel are
 //     every CH-th byte of the image (the channel tasks' stores meet in L2 before the lines go to memory);
 //   * narrow windows: the vector work of a step goes out over the column pass's NKB triples (the hand-off in
 //     slots 0 .. 7, the emission in 1 .. 4, the staging from slot 5 on) and the stores over the row pass's first four blocks.
@@ -105,7 +106,7 @@ template <int NKB> struct FwCfg {
     static constexpr int LDS = QOFF + 2 * 2 * 32 * 4;
 };
 
-// Whole-frame partial sums of the quirk for a 1- or 4-channel image (fc_prepass), read by fw_blur_u8<NKB, true, 1 / 4>:
+// Whole-frame partial sums of the quirk for a 1-, 2- or 4-channel image (fc_prepass), read by fw_blur_u8<NKB, true, 1 / 2 / 4>:
 //   srow [frame][row][CH]             Srow(r, c) = sum_x wx(x) img[r][x][c]          (complete: the batches add with atomics)
 //   cpart[frame][band][cpitch]        sum over the band's rows of wy(r) img[r][x][c] at CH x + c
 //   zsum [frame][CH]                  Z(c) = sum_r wy(r) Srow(r, c)                  (complete, 64-bit)
@@ -118,7 +119,7 @@ struct FcQuirk {
     float dr, dc;
 };
 
-// the quirk's sums the kernel reads: fx_prepass's for three channels, fc_prepass's for one and four
+// the quirk's sums the kernel reads: fx_prepass's for three channels, fc_prepass's for one, two and four
 template <int CH> using FwQuirk = std::conditional_t<CH == 3, FxQuirk, FcQuirk>;
 
 // dwords of a row per pre-pass thread: batches of 256 G dwords (G = 1, 2, 4); as many batches as the row needs
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
                                                      int chunks, int tps, int nseg, int ntasks, FwQuirk<CH> qk, const uint8_t* __restrict__ strips, FwChSel chsel, FwPitch pt,
                                                      FwFrameList<FRAMES> ft)
 {
-    static_assert(CH == 1 || CH == 3 || CH == 4, "one, three or four channels");
+    static_assert(CH >= 1 && CH <= 4, "one to four channels");
     using C = FwCfg<NKB>;
     constexpr int PADA = C::PADA, PW = C::PW, NT = C::NT, PER = C::PER;
     constexpr int RS = NKB > 4 ? NKB : 4;                         // row-pass slots: the stores of the previous tile need four
@@ -284,6 +285,10 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
             const uint32_t o = in ? off + static_cast<uint32_t>(32 * CH * k) : off;
             if constexpr (CH == 1) {
                 raw[k][0] = __builtin_amdgcn_raw_buffer_load_b32(rimg, o, 0, 0);
+            } else if constexpr (CH == 2) {
+                typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+                const u2 t = __builtin_amdgcn_raw_buffer_load_b64(rimg, o, 0, 0);
+                raw[k][0] = t[0]; raw[k][1] = t[1];
             } else if constexpr (CH == 3) {
                 typedef uint32_t u3 __attribute__((ext_vector_type(3)));
                 const u3 t = __builtin_amdgcn_raw_buffer_load_b96(rimg, in ? off + 32u * CH * k : off, 0, 0);
@@ -305,10 +310,12 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
         }
     };
     // channel c of group k -> binary16 subnormals -> LDS: two v_perm_b32 and one ds_write_b64.  CH = 3: pixels (0, 1) of the group
-    // are bytes (c, 3 + c), pixels (2, 3) bytes (6 + c, 9 + c) of its three dwords; CH = 4: byte c of each dword
+    // are bytes (c, 3 + c), pixels (2, 3) bytes (6 + c, 9 + c) of its three dwords; CH = 4: byte c of each dword; CH = 2: one
+    // v_perm_b32 per dword, bytes (c, 2 + c) of it
     const uint32_t selA = CH == 3 ? (c == 0 ? 0x0c030c00u : (c == 1 ? 0x0c040c01u : 0x0c050c02u))                 // operands (d1, d0)
                                   : 0x0c000c00u | (static_cast<uint32_t>(4 + c) << 16) | static_cast<uint32_t>(c);  // CH = 4: (d1, d0), (d3, d2)
     const uint32_t selB = c == 0 ? 0x0c050c02u : (c == 1 ? 0x0c060c03u : 0x0c070c00u);                             // CH = 3: (d2, d1) / c == 2: (d2, d2)
+    const uint32_t selC = 0x0c000c00u | (static_cast<uint32_t>(2 + c) << 16) | static_cast<uint32_t>(c);             // CH = 2: (0, d0), (0, d1)
     auto commit_item = [&](int buf, int k) __attribute__((always_inline)) {
         if (k >= PER) return;
         // (groups past the window's GPR of the last k hold whatever their clamped load returned: they land in the row's padding)
@@ -317,6 +324,9 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
         if constexpr (CH == 1) {
             wd.x = __builtin_amdgcn_perm(0u, raw[k][0], 0x0c010c00u);
             wd.y = __builtin_amdgcn_perm(0u, raw[k][0], 0x0c030c02u);
+        } else if constexpr (CH == 2) {
+            wd.x = __builtin_amdgcn_perm(0u, raw[k][0], selC);
+            wd.y = __builtin_amdgcn_perm(0u, raw[k][1], selC);
         } else if constexpr (CH == 3) {
             wd.x = __builtin_amdgcn_perm(raw[k][1], raw[k][0], selA);
             wd.y = __builtin_amdgcn_perm(raw[k][2], c == 2 ? raw[k][2] : raw[k][1], selB);
@@ -401,7 +411,7 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
             fx_swap4(hp[4 * hf], hp[4 * hf + 2], hp[4 * hf + 1], hp[4 * hf + 3], lp[4 * hf], lp[4 * hf + 2], lp[4 * hf + 1], lp[4 * hf + 3]);
         }
     };
-    // E: four registers of the finished tile (rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column) -> bytes, kept in rr[gq].  CH = 3,
+    // E: four registers of the finished tile (rows 8 gq + 4 h + 0 .. 3 of the lane's pixel column) -> bytes, kept in rr[gq].  CH = 2, 3,
     // 4: no transposes, the lane keeps its COLUMN, so a store instruction covers 2 rows x 32 pixels.  CH = 1: transposed inside the
     // lane quad: lane q of quad Q holds row 8 gq + 4 h + q, pixels 4 Q .. 4 Q + 3 of the wave's 32
     const uint32_t sel1 = (lane & 1) ? 0x03070105u : 0x06020400u, sel2 = (lane & 2) ? 0x03020706u : 0x05040100u;
@@ -483,7 +493,7 @@ __global__ __launch_bounds__(256, 1) void fw_blur_u8(const uint8_t* __restrict__
             }
         } else {                                                          // byte c of every pixel, rows 8 gq + 4 h + k of the lane's column
             int row0 = 32 * tile + 8 * gq + 4 * h;
-            if constexpr (CH == 4) asm volatile("" : "+v"(row0));
+            if constexpr (CH == 4 || CH == 2) asm volatile("" : "+v"(row0));
             const uint32_t base = CH == 3 ? lane_out + static_cast<uint32_t>(32 * tile + 8 * gq) * rowstep
                                           : static_cast<uint32_t>(row0) * rowstep + static_cast<uint32_t>(xcol) * CH + static_cast<uint32_t>(c);
 #pragma unroll
@@ -583,6 +593,27 @@ template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* s
     return hipGetLastError();
 }
 
+// two channels: fw_launch without the instantiations for a frame list (no entry with one sigma per frame takes two channels)
+template <int NKB> hipError_t fw_launch2(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FcQuirk* qk,
+                                         const uint8_t* strips, FwChSel chsel, FwPitch pt)
+{
+    using C = FwCfg<NKB>;
+    const int nact = fw_chsel_count(chsel);
+    if (nact < 1 || nact > 2) return hipErrorInvalidValue;
+    for (int i = 0; i < nact; ++i)
+        if (static_cast<int>((chsel >> (4 + 2 * i)) & 3u) >= 2) return hipErrorInvalidValue;
+    const FxLaunch l = fx_plan_launch(g, nact, C::NT, num_cus);
+    if (l.ntasks == 0) return hipSuccess;
+    static std::atomic<unsigned long long> attr_done{ 0 };
+    const hipError_t e = fx_set_lds(attr_done, C::LDS, fw_blur_u8<NKB, true, 2>, fw_blur_u8<NKB, false, 2>);
+    if (e != hipSuccess) return e;
+    const mx_half8* fr = static_cast<const mx_half8*>(frags);
+    const int nt = static_cast<int>(l.ntasks);
+    if (qk) hipLaunchKernelGGL((fw_blur_u8<NKB, true, 2>), l.grid, dim3(256), C::LDS, st, src, dst, fr, g, l.chunks, l.tps, l.nseg, nt, *qk, strips, chsel, pt, FwNoFrames{});
+    else hipLaunchKernelGGL((fw_blur_u8<NKB, false, 2>), l.grid, dim3(256), C::LDS, st, src, dst, fr, g, l.chunks, l.tps, l.nseg, nt, FcQuirk{}, strips, chsel, pt, FwNoFrames{});
+    return hipGetLastError();
+}
+
 // the three-channel entry (FxEntry; fx_registry.hpp: find_entry_for_pad) of the wide windows
 template <int NKB> hipError_t fw_launch_u8c3(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk,
                                              const uint8_t* strips, float* vdump, unsigned long long* stamps)
@@ -593,7 +624,7 @@ template <int NKB> hipError_t fw_launch_u8c3(hipStream_t st, const uint8_t* src,
 
 struct FcEntry {
     int nkb;
-    // ch: 1 or 4; qk: the quirk's sums (null: nyquist_quirk = 0); chsel: the channels to blur; pt: where the rows and frames lie;
+    // ch: 1, 2 or 4; qk: the quirk's sums (null: nyquist_quirk = 0); chsel: the channels to blur; pt: where the rows and frames lie;
     // ft: the frame list of a launch over frames with their own sigmas, or null (FwFrame)
     hipError_t (*blur_u8)(hipStream_t, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk, const uint8_t* strips,
                           FwChSel chsel, FwPitch pt, const FwFrame* ft);
@@ -612,12 +643,14 @@ template <int NKB> hipError_t fw_launch_u8c3_sel(hipStream_t st, const uint8_t* 
     return fw_launch<NKB, 3>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
 }
 
-// the one- and four-channel entry (FcEntry; fx_registry.hpp: find_entry) of every window class
+// the one-, two- and four-channel entry (FcEntry; fx_registry.hpp: find_entry) of every window class (two channels: the chroma plane
+// of an NV12 surface -- blur_gaussian_nv12_*; no public entry takes channels = 2)
 template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk,
                                               const uint8_t* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
 {
     if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
     if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
+    if (ch == 2) return ft ? hipErrorInvalidValue : fw_launch2<NKB>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt);
     return hipErrorInvalidValue;
 }
 
@@ -638,6 +671,13 @@ __device__ __forceinline__ void fc_edge_strips_body(const uint8_t* __restrict__ 
     const int r = i / dpr, d = i - r * dpr;
     const uint8_t* line = src + static_cast<size_t>(f) * sframe + static_cast<size_t>(r) * spitch;
     uint32_t o = 0;
+    if constexpr (CH == 2) {                                           // two pixels per dword, each mirrored on its own, byte by byte
+        const int X2 = x0 - pada + 2 * d;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o |= static_cast<uint32_t>(line[2 * mx_refl(X2 + (k >> 1), cols) + (k & 1)]) << (8 * k);
+        *reinterpret_cast<uint32_t*>(strips + ((static_cast<size_t>(f) * (nleft + nright) + sidx) * rows + r) * (CH * win) + 4 * d) = o;
+        return;
+    }
     const int X = x0 - pada + (CH == 1 ? 4 * d : d);                   // first pixel of the dword's window position
     if (CH == 4) o = *reinterpret_cast<const uint32_t*>(line + 4 * mx_refl(X, cols));
     else if (X >= 0 && X + 3 < cols) o = *reinterpret_cast<const uint32_t*>(line + X);
@@ -649,7 +689,8 @@ __device__ __forceinline__ void fc_edge_strips_body(const uint8_t* __restrict__ 
 }
 
 // The quirk's sums (FcQuirk) for a CH-channel image: workgroup (band of band_rows rows, batch of 256 G dwords of a row, frame).
-// A thread owns G dwords of every row of the band: CH = 1 four pixels, CH = 4 one pixel's four channels.  Exact integers; srow and
+// A thread owns G dwords of every row of the band: CH = 1 four pixels, CH = 2 two pixels' two channels (byte k of the dword: pixel
+// k / 2, channel k % 2), CH = 4 one pixel's four channels.  Exact integers; srow and
 // zsum must be zero before the launch (they are completed with atomics).  sred[row][channel][lane]: lane l of every wave adds
 // into slot l (fx_altsums_body).  chmask: the channels whose sums the launch that follows reads (bit c; one sigma per channel: a
 // subset) -- the row sums of the others are neither reduced nor added up (srow and zsum stay 0 for them).
@@ -676,7 +717,7 @@ __device__ __forceinline__ void fc_altsums_body(const uint8_t* __restrict__ src,
         back[j] = dj[j] == ndw - 1 ? over : 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int b = 4 * dj[j] + k, x = CH == 1 ? b : dj[j];          // pixel of byte k of the dword
+            const int b = 4 * dj[j] + k, x = CH == 1 ? b : (CH == 2 ? b >> 1 : dj[j]);          // pixel of byte k of the dword (CH = 2: two pixels per dword)
             wx[j][k] = dj[j] < ndw && b < static_cast<int>(rowbytes) ? mx_alt_weight(x, cols, pad) : 0;
             col[j][k] = 0;
         }

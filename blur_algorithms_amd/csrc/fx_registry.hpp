@@ -4,10 +4,11 @@
 //   pad    8  24  40  56  72  88  104  120  136  152  168
 // Each family has one instantiation unit, which the Makefile compiles once per class (-DBLUR_INST_NKB) into build/<family>_conv_<NKB>.o:
 //   fx_conv.hip   fx_kernels.hpp, three channels per workgroup, NKB <= 11: FxEntry
-//   fw_conv.hip   fw_kernels.hpp, one channel per workgroup, every class: FcEntry (one and four channels) and Fw3Entry (three channels,
-//                 a subset per launch: one sigma per channel); NKB >= 13 also FxEntry (whole BGR frames, pad 73 .. 168)
+//   fw_conv.hip   fw_kernels.hpp, one channel per workgroup, every class: FcEntry (one, two and four channels; two: the Cb/Cr plane
+//                 of an NV12 surface) and Fw3Entry (three channels, a subset per launch: one sigma per channel); NKB >= 13 also
+//                 FxEntry (whole BGR frames, pad 73 .. 168)
 //   ff_conv.hip   ff_kernels.hpp, every class, once per pixel type as well (-DBLUR_INST_T; build/ff_[u16_|f16_|bf16_]conv_<NKB>.o):
-//                 FfEntryT<T> for float, uint16_t, ff_f16 and ff_bf16
+//                 FfEntryT<T> for float, uint16_t (also two channels: P016), ff_f16 and ff_bf16
 //   mx_conv.hip   mx_kernels.hpp, every class: MxEntry
 // This header names no entry type and needs no kernel header: engine.hip includes ff_kernels.hpp well after it.
 #pragma once

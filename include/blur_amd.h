@@ -535,7 +535,47 @@ int blur_gaussian_bf16_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d
                                                 size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
                                                 const double* sigmas, const blur_opts* opts);
 
-/* host-only plan of the calls above (no GPU needed; the same host code the entries use): for channel c, out[3 c] = its group (the
+/* ---- decoded video surfaces: NV12 (8-bit) and P010 / P016 (16-bit), DEVICE pointers -------------------------------------------
+   What rocDecode, VA-API and the other decoders produce: a rows x cols luma plane and a rows / 2 x cols / 2 plane of interleaved
+   Cb/Cr pairs (cols samples per chroma row), both with the same row pitch.  The planes are passed separately (in a decoder
+   surface d_src_uv = d_src_y + surface_height * pitch), so the entries do not care how many rows of padding lie between them.
+   A call blurs the luma plane with sigmas[0], Cb with sigmas[1] and Cr with sigmas[2], each sigma in pixels OF THE PLANE IT
+   APPLIES TO (the same blur in luma pixels on all three is (s, s / 2, s / 2)); nothing is split, converted or repacked: the
+   chroma plane runs on the two-channel instantiation of the fused kernel.
+     result   the luma plane is, bit for bit, what blur_gaussian_u8_pitched_batch_dev (p016: ..._u16_...) returns for that plane
+              with channels = 1 and sigmas[0]; Cb (Cr) is, bit for bit, what that entry returns for the de-interleaved rows / 2 x
+              cols / 2 Cb (Cr) plane with sigmas[1] (sigmas[2]).
+     zero     sigmas[p] == 0 leaves the plane or channel as it is: copied out of place, untouched in place.
+     p016     samples are uint16_t, pitches and strides in BYTES; the output follows the u16 rule (uint16_t)((uint32_t)(int32_t)(v +
+              0.5f) & 0xffff).  The low bits of P010 data (10 significant bits in the HIGH bits of the word, the low 6 zero) are NOT
+              masked: a blurred P010 surface has non-zero low bits, which a P010 consumer ignores and a P016 consumer uses.
+     writes   no byte outside the rows x cols and rows / 2 x cols rectangles is written (padding between rows and planes stays).
+     overlap  per plane as for the pitched entries: an in-place call (d_dst_y == d_src_y, d_dst_uv == d_src_uv, equal pitches) and
+              overlapping spans read from one gathered copy.  The destination of one plane must not overlap the source of the other.
+     engine   per plane, the one-channel entries' rules: AUTO takes the fused kernel wherever they give one to that pad (nv12: pad
+              <= 168; p016: pad <= 104), FUSED fails with BLUR_ERR_UNSUPPORTED, before anything is written, where a blurred plane has
+              no fused kernel, FFT takes the plane path.  blur_last_engine reports 6 if every blurred plane ran fused, else 0 with a
+              note naming the planes on the plane path.
+   BLUR_ERR_INVALID: a NULL pointer (sigmas included), nframes < 0, rows or cols <= 0 or odd, a pitch below cols * sizeof(sample)
+   or no multiple of sizeof(sample), with nframes > 1 a frame stride below its plane's span ((plane rows - 1) * pitch + cols *
+   sizeof(sample)) or no multiple of sizeof(sample), a negative, NaN or infinite sigma.  BLUR_ERR_UNSUPPORTED: the luma pad exceeds
+   min(rows, cols) - 1 or a chroma pad exceeds min(rows / 2, cols / 2) - 1.  Checked in this order before the device is touched (ctx
+   may then be NULL); nframes == 0 is a no-op.  The _host entries take one PACKED surface in host memory: rows * cols luma samples,
+   then rows / 2 rows of cols chroma samples (src and dst apart or equal). */
+int blur_gaussian_nv12_batch_dev(blur_ctx* ctx, const uint8_t* d_src_y, const uint8_t* d_src_uv, size_t src_pitch, size_t src_y_frame_stride,
+                                 size_t src_uv_frame_stride, uint8_t* d_dst_y, uint8_t* d_dst_uv, size_t dst_pitch, size_t dst_y_frame_stride,
+                                 size_t dst_uv_frame_stride, int nframes, int rows, int cols, const double* sigmas, const blur_opts* opts);
+int blur_gaussian_nv12_dev(blur_ctx* ctx, const uint8_t* d_src_y, const uint8_t* d_src_uv, size_t src_pitch, uint8_t* d_dst_y, uint8_t* d_dst_uv,
+                           size_t dst_pitch, int rows, int cols, const double* sigmas, const blur_opts* opts);
+int blur_gaussian_nv12_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int rows, int cols, const double* sigmas, const blur_opts* opts);
+int blur_gaussian_p016_batch_dev(blur_ctx* ctx, const uint16_t* d_src_y, const uint16_t* d_src_uv, size_t src_pitch, size_t src_y_frame_stride,
+                                 size_t src_uv_frame_stride, uint16_t* d_dst_y, uint16_t* d_dst_uv, size_t dst_pitch, size_t dst_y_frame_stride,
+                                 size_t dst_uv_frame_stride, int nframes, int rows, int cols, const double* sigmas, const blur_opts* opts);
+int blur_gaussian_p016_dev(blur_ctx* ctx, const uint16_t* d_src_y, const uint16_t* d_src_uv, size_t src_pitch, uint16_t* d_dst_y, uint16_t* d_dst_uv,
+                           size_t dst_pitch, int rows, int cols, const double* sigmas, const blur_opts* opts);
+int blur_gaussian_p016_host(blur_ctx* ctx, const uint16_t* src, uint16_t* dst, int rows, int cols, const double* sigmas, const blur_opts* opts);
+
+/* host-only plan of the _sigmas_ entries (no GPU needed; the same host code the entries use): for channel c, out[3 c] = its group (the
    channels of equal sigma share an index, counted in the order of their first channel; -1 for sigma = 0), out[3 c + 1] = the pad
    of its sigma on this frame, out[3 c + 2] = the fused kernel's window class NKB, 8 (NKB - 4) < pad <= 8 (NKB - 2), or 0 where the
    pad has no fused kernel (pad > 168).  Status as the entries above; BLUR_ERR_INVALID also for a null `out`. */

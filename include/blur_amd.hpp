@@ -351,6 +351,21 @@ inline void gaussian_blur_bf16_dev(const uint16_t* d_src, size_t src_step, uint1
     if (!ctx) ctx = default_ctx();
     check(ctx, blur_gaussian_bf16_sigmas_pitched_batch_dev(ctx, d_src, src_step, 0, d_dst, dst_step, 0, 1, rows, cols, channels, sigmas, opts), "gaussian_blur_bf16_dev");
 }
+// A decoded video surface on the device, where it lies: NV12 (8-bit) or P010 / P016 (16-bit).  d_*_y: the rows x cols luma plane,
+// d_*_uv: the rows / 2 x cols / 2 plane of interleaved Cb/Cr pairs, both `step` bytes per row (blur_amd.h: blur_gaussian_nv12_dev).
+// sigmas: (Y, Cb, Cr), each in pixels of its own plane; 0 leaves the plane or channel as it is.  The destination may be the source.
+inline void gaussian_blur_nv12_dev(const uint8_t* d_src_y, const uint8_t* d_src_uv, size_t src_step, uint8_t* d_dst_y, uint8_t* d_dst_uv, size_t dst_step, int rows,
+                                   int cols, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_nv12_dev(ctx, d_src_y, d_src_uv, src_step, d_dst_y, d_dst_uv, dst_step, rows, cols, sigmas, opts), "gaussian_blur_nv12_dev");
+}
+inline void gaussian_blur_p016_dev(const uint16_t* d_src_y, const uint16_t* d_src_uv, size_t src_step, uint16_t* d_dst_y, uint16_t* d_dst_uv, size_t dst_step, int rows,
+                                   int cols, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_p016_dev(ctx, d_src_y, d_src_uv, src_step, d_dst_y, d_dst_uv, dst_step, rows, cols, sigmas, opts), "gaussian_blur_p016_dev");
+}
 
 // pocketfft_1D(image, sigma) (Source.cpp:280-392) and pocketfft_2D(image, sigma) (Source.cpp:143-277): the two
 // pocketfft paths multiply all N/2+1 bins with the kernel's own spectrum (no Nyquist-slot quirk) and, inside the
