@@ -158,6 +158,19 @@ SYMBOLS = {
         C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
     "blur_gaussian_f32_frame_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
         C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_u16_frame_sigmas_batch_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_frame_sigmas_batch_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_frame_sigmas_batch_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_u16_frame_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_f16_frame_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_bf16_frame_sigmas_pitched_batch_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_nv12_frame_sigmas_batch_dev": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
+        C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
+    "blur_gaussian_p016_frame_sigmas_batch_dev": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
+        C.c_int, C.POINTER(C.c_double), C.POINTER(BlurOpts)]),
     "blur_gaussian_frame_sigmas_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "blur_fastboxblur_u8_batch_multi_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "blur_fastboxblur_u8_batch_multi_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -286,6 +286,28 @@ def _nv12_sigmas(sigma):
     return vals
 
 
+def _nv12_frame_sigmas(sigmas, y):
+    """the (luma, chroma) sigmas of every frame of a gaussian_nv12_per_frame call on the clip y [n, rows, cols], each in pixels of its
+    own plane: an entry that is a number s means (s, s / 2), a pair is taken as given"""
+    if len(y.shape) != 3:
+        raise ValueError("expected a clip: y [n, rows, cols] with uv [n, rows / 2, cols / 2, 2]")
+    if not _is_sigma_sequence(sigmas):
+        raise ValueError("sigmas: expected a sequence with one entry per frame")
+    pairs = []
+    for f, e in enumerate(sigmas):
+        if not _is_sigma_sequence(e):
+            s = float(e)
+            pairs.append((s, s / 2))
+            continue
+        vals = tuple(float(v) for v in e)
+        if len(vals) != 2:
+            raise ValueError("sigmas[%d]: expected a number or a pair (sigma_y, sigma_c), got %d values" % (f, len(vals)))
+        pairs.append(vals)
+    if len(pairs) != y.shape[0]:
+        raise ValueError("sigmas: expected one entry per frame (%d), got %d" % (y.shape[0], len(pairs)))
+    return pairs
+
+
 def _nv12_tensors(y, uv, out, require_cuda=True):
     """the checks of BlurContext.gaussian_nv12 on its tensors, before the library is called: (y, uv, y_out, uv_out, source layout,
     result layout), the layouts as _nv12_layout returns them.  uint8 is NV12, uint16 P016"""
@@ -306,6 +328,13 @@ def _nv12_tensors(y, uv, out, require_cuda=True):
             raise ValueError("out must match the input: (y_out, uv_out) with the shapes, dtype and device of (y, uv)")
     dl = _nv12_layout(yo.shape, yo.stride(), uvo.shape, uvo.stride())
     return y, uv, yo, uvo, sl, dl
+
+
+def _nv12_per_frame_tensors(y, uv, sigmas, out, require_cuda=True):
+    """the checks of BlurContext.gaussian_nv12_per_frame on its tensors and sigmas, before the library is called: what _nv12_tensors
+    returns, and the (luma, chroma) sigmas per frame"""
+    r = _nv12_tensors(y, uv, out, require_cuda)
+    return r + (_nv12_frame_sigmas(sigmas, y),)
 
 
 def _is_sigma_sequence(sigma):
@@ -816,6 +845,60 @@ class BlurContext:
         power-of-two scale comes from its own max|x|), for 1, 3 and 4 channels (blur_gaussian_f32_frame_sigmas_batch_dev)."""
         return self._gaussian_per_frame(frames, sigmas, out, nyquist_quirk, engine, np.float32, "f32")
 
+    def gaussian_u16_per_frame(self, frames, sigmas, out=None, nyquist_quirk=True, engine=None):
+        """gaussian_per_frame for uint16 frames (torch.uint16 or numpy uint16): frame f is, bit for bit, what gaussian_u16() returns for
+        it alone with sigmas[f], for 1, 3 and 4 channels (blur_gaussian_u16_frame_sigmas_batch_dev)."""
+        return self._gaussian_per_frame(frames, sigmas, out, nyquist_quirk, engine, np.uint16, "u16")
+
+    def gaussian_f16_per_frame(self, frames, sigmas, out=None, nyquist_quirk=True, engine=None):
+        """gaussian_per_frame for float16 frames (torch.float16 or numpy float16): frame f is, bit for bit, what gaussian_f16() returns
+        for it alone with sigmas[f] (its power-of-two scale comes from its own max|x|), for 1, 3 and 4 channels
+        (blur_gaussian_f16_frame_sigmas_batch_dev)."""
+        return self._gaussian_per_frame(frames, sigmas, out, nyquist_quirk, engine, np.float16, "f16")
+
+    def gaussian_bf16_per_frame(self, frames, sigmas, out=None, nyquist_quirk=True, engine=None):
+        """gaussian_per_frame for bfloat16 frames (torch.bfloat16; a CPU tensor takes the host route): frame f is, bit for bit, what
+        gaussian_bf16() returns for it alone with sigmas[f] (its power-of-two scale comes from its own max|x|), for 1, 3 and 4
+        channels (blur_gaussian_bf16_frame_sigmas_batch_dev)."""
+        return self._gaussian_per_frame(frames, sigmas, out, nyquist_quirk, engine, BF16, "bf16")
+
+    def gaussian_nv12_per_frame(self, y, uv, sigmas, out=None, nyquist_quirk=True, engine=None):
+        """Gaussian blur of a decoded clip with its own sigmas per FRAME (a focus pull, a blur ramp): NV12 (uint8) or P010 / P016
+        (uint16).  y is [n, rows, cols], uv [n, rows / 2, cols / 2, 2], with the views and layout rules of gaussian_nv12.  `sigmas`
+        is a sequence of n entries, each a number s -- (s, s / 2): the same blur in luma pixels on luma and chroma -- or a pair
+        (sigma_y, sigma_c), each in pixels of its own plane; sigma_c blurs Cb and Cr alike, and a 0 leaves that plane of that frame
+        as it is.  The planes of frame f are, bit for bit, what gaussian_nv12() returns for that frame alone with (sigma_y, sigma_c,
+        sigma_c) (blur_gaussian_nv12_frame_sigmas_batch_dev, blur_gaussian_p016_frame_sigmas_batch_dev: per plane, the frames of one
+        window class share one launch).  engine: None (the library's choice), "fused" or "fft", per plane and frame.
+
+        torch CUDA tensors: asynchronous on torch's current stream; out=(y_out, uv_out) or, by default, in place; returns (y_out,
+        uv_out).  numpy arrays (contiguous): host round trip frame by frame through the scalar entry, returns new arrays (or
+        `out`).  ValueError, before the library is called: what gaussian_nv12 refuses, y that is not [n, rows, cols], sigmas of
+        another length than n, an entry that is neither a number nor a pair.
+        """
+        if isinstance(y, np.ndarray) or isinstance(uv, np.ndarray):
+            if not (isinstance(y, np.ndarray) and isinstance(uv, np.ndarray)):
+                raise ValueError("expected uint8 (NV12) or uint16 (P016) arrays y and uv")
+            pairs = _nv12_frame_sigmas(sigmas, y)
+            n = y.shape[0]
+            if len(uv.shape) != 4 or uv.shape[0] != n:
+                raise ValueError("uv must be [n, rows / 2, cols / 2, 2] for y [n, rows, cols]")
+            yo, uvo = (np.empty_like(np.ascontiguousarray(y)), np.empty_like(np.ascontiguousarray(uv))) if out is None else out
+            for f in range(n):
+                sy, sc = pairs[f]
+                self.gaussian_nv12(y[f:f + 1], uv[f:f + 1], (sy, sc, sc), out=(yo[f:f + 1], uvo[f:f + 1]), nyquist_quirk=nyquist_quirk, engine=engine)
+            return yo, uvo
+        y, uv, yo, uvo, sl, dl, pairs = _nv12_per_frame_tensors(y, uv, sigmas, out)
+        n, rows, cols = sl[:3]
+        sg = (C.c_double * max(1, 2 * n))(*[v for p in pairs for v in p])
+        o = self._opts(nyquist_quirk, engine=engine)
+        es = y.element_size()
+        self.use_torch_stream()
+        entry = self._lib.blur_gaussian_nv12_frame_sigmas_batch_dev if es == 1 else self._lib.blur_gaussian_p016_frame_sigmas_batch_dev
+        self._check(entry(self._h, y.data_ptr(), uv.data_ptr(), sl[3] * es, sl[4] * es, sl[5] * es, yo.data_ptr(), uvo.data_ptr(), dl[3] * es, dl[4] * es, dl[5] * es,
+                          n, rows, cols, sg, C.byref(o)))
+        return yo, uvo
+
     def _gaussian_per_frame(self, frames, sigmas, out, nyquist_quirk, engine, dtype, tname):
         o = self._opts(nyquist_quirk, engine=engine)
         vals = [float(v) for v in sigmas]
@@ -833,6 +916,7 @@ class BlurContext:
                     res[f] = a[f]
                 else:
                     self._check(host_entry(self._h, a[f].ctypes.data, res[f].ctypes.data, rows, cols, ch, vals[f], C.byref(o)))
+            res = _gauss_result(res, out, dtype)
             return res if frames.ndim == 4 or out is not None else res[..., 0]
         import torch
         t4 = frames.unsqueeze(-1) if isinstance(frames, torch.Tensor) and frames.dim() == 3 else frames

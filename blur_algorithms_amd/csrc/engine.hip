@@ -1845,8 +1845,10 @@ static int run_fc_u8(blur_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int nf
                             : (G == 1 ? fc_prepass<4, 1> : (G == 2 ? fc_prepass<4, 2> : fc_prepass<4, 4>));
         auto kern_frames = ch == 1 ? (G == 1 ? fc_prepass_frames<1, 1> : (G == 2 ? fc_prepass_frames<1, 2> : fc_prepass_frames<1, 4>))
                                    : (G == 1 ? fc_prepass_frames<4, 1> : (G == 2 ? fc_prepass_frames<4, 2> : fc_prepass_frames<4, 4>));
-        if (ft && ch == 2) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for 2 channels: no launch over frames with their own sigmas");
-        if (ft)
+        if (ft && ch == 2)          // (the two-channel instantiations are fc_frames2.hip's)
+            HIP_TRY(ctx, fc_prepass_frames2_launch(G, static_cast<unsigned>(n_alt + n_strip), ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, pada, nbands,
+                                                   nbatches, cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel), pt.src_pitch, pt.src_frame, ft));
+        else if (ft)
             hipLaunchKernelGGL(kern_frames, dim3(n_alt + n_strip), dim3(256), 0, ctx->stream, d_src, srow, cpart, zsum, ctx->fx_strips, rows, cols, pada, nbands, nbatches,
                                cpitch, n_alt, chunks_x, g.nright, strip_blocks, band_rows, fw_chsel_bits(chsel), pt.src_pitch, pt.src_frame, ft);
         else
@@ -1923,11 +1925,13 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
                                    : (ch == 3 ? pick(ff_prepass_frames<T, 3, 1>, ff_prepass_frames<T, 3, 2>, ff_prepass_frames<T, 3, 4>)
                                               : pick(ff_prepass_frames<T, 4, 1>, ff_prepass_frames<T, 4, 2>, ff_prepass_frames<T, 4, 4>));
         auto fin = ch == 1 ? ff_finalize<1> : (ch == 3 ? ff_finalize<3> : ff_finalize<4>);
-        if constexpr (u16) {                  // two channels (the chroma plane of a P016 surface, blur_nv_batch_impl): u16 only, no frame lists
+        auto fin_frames = ch == 1 ? ff_finalize_frames<1> : (ch == 3 ? ff_finalize_frames<3> : ff_finalize_frames<4>);
+        if constexpr (u16) {                  // two channels (the chroma plane of a P016 surface, blur_nv_batch_impl and blur_nv_frame_sigmas_batch_impl): u16 only
             if (ch == 2) {
-                if (ft) return fail(ctx, BLUR_ERR_UNSUPPORTED, "fused kernel for 2 channels: no launch over frames with their own sigmas");
                 kern = pick(ff_prepass<T, 2, 1>, ff_prepass<T, 2, 2>, ff_prepass<T, 2, 4>);
+                kern_frames = pick(ff_prepass_frames<T, 2, 1>, ff_prepass_frames<T, 2, 2>, ff_prepass_frames<T, 2, 4>);
                 fin = ff_finalize<2>;
+                fin_frames = ff_finalize_frames<2>;
             }
         }
         if (n_alt + n_strip > 0 && ft)
@@ -1938,7 +1942,6 @@ static int run_ff(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows
                                nbatches, ne, n_alt, chunks_x, g.nright, strip_blocks, band_rows, quirk ? 1 : 0, pt.src_pitch, pt.src_frame);
         HIP_TRY(ctx, hipGetLastError());
         if (quirk) {
-            auto fin_frames = ch == 1 ? ff_finalize_frames<1> : (ch == 3 ? ff_finalize_frames<3> : ff_finalize_frames<4>);
             if (ft) hipLaunchKernelGGL(fin_frames, dim3(nframes), dim3(256), 0, ctx->stream, spart, srow, zsum, rows, nbatches, ft);
             else hipLaunchKernelGGL(fin, dim3(nframes), dim3(256), 0, ctx->stream, spart, srow, zsum, rows, p.sz.pad, nbatches);
             HIP_TRY(ctx, hipGetLastError());
@@ -2504,7 +2507,9 @@ struct NvSurface {
 
 // The arguments of every blur_gaussian_{nv12,p016}_* entry, without a context or a device (es: bytes per sample): the status and,
 // where it is not BLUR_OK, its text in *why.  Layout errors come before BLUR_ERR_UNSUPPORTED.
-static int nv_status(const NvSurface& s, size_t es, int nframes, int rows, int cols, const double* sigmas, const char** why)
+// nv_layout_status: the part that does not read sigmas (pointers, sizes, pitches, strides); nv_status: a call with one sigma per
+// plane and channel; nv_frame_sigmas_status (below): one luma and one chroma sigma per frame
+static int nv_layout_status(const NvSurface& s, size_t es, int nframes, int rows, int cols, const double* sigmas, const char** why)
 {
     auto no = [&](int rc, const char* text) { *why = text; return rc; };
     if (!s.sy || !s.suv || !s.dy || !s.duv || !sigmas || nframes < 0) return no(BLUR_ERR_INVALID, "null plane or sigmas pointer, or negative frame count");
@@ -2518,6 +2523,13 @@ static int nv_status(const NvSurface& s, size_t es, int nframes, int rows, int c
             s.suv_frame < ch_frame_span(rows / 2, s.spitch, rowbytes) || s.duv_frame < ch_frame_span(rows / 2, s.dpitch, rowbytes))
             return no(BLUR_ERR_INVALID, "frame stride below its plane's span: the planes of the batch would overlap");
     }
+    return BLUR_OK;
+}
+
+static int nv_status(const NvSurface& s, size_t es, int nframes, int rows, int cols, const double* sigmas, const char** why)
+{
+    auto no = [&](int rc, const char* text) { *why = text; return rc; };
+    if (int rc = nv_layout_status(s, es, nframes, rows, cols, sigmas, why)) return rc;
     for (int p = 0; p < 3; ++p)
         if (!(sigmas[p] >= 0) || !std::isfinite(sigmas[p])) return no(BLUR_ERR_INVALID, "every sigma must be finite and positive, or 0 for a plane that is left as it is");
     for (int p = 0; p < 3; ++p) {
@@ -2592,7 +2604,7 @@ static int blur_nv_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols,
 }
 
 // ======================================================================================
-// One sigma per frame (blur_gaussian_{u8,f32}_frame_sigmas_*): frame f is what the scalar entry returns for it alone with
+// One sigma per frame (blur_gaussian_{u8,f32,u16,f16,bf16}_frame_sigmas_*): frame f is what the scalar entry returns for it alone with
 // sigmas[f]; sigma = 0 copies the frame
 // ======================================================================================
 // The frames of a call by sigma and by window class.  slot: the distinct positive sigmas in the order of their first frame (frames
@@ -2607,10 +2619,12 @@ struct FrameSigmaPlan {
 
 // The arguments of every blur_gaussian_*_frame_sigmas_* entry, without a context or a device: the status and, where it is not
 // BLUR_OK, its text in *why.  Every entry of sigmas is checked here, before anything is launched: a refused call has written nothing.
-static int frame_sigmas_status(const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, FrameSigmaPlan& pl, const char** why)
+// two_ok: two channels are legal (the chroma plane of an NV12 / P016 surface: blur_nv_frame_sigmas_batch_impl only)
+static int frame_sigmas_status(const void* src, const void* dst, int nframes, int rows, int cols, int channels, const double* sigmas, FrameSigmaPlan& pl, const char** why,
+                               bool two_ok = false)
 {
     auto no = [&](int rc, const char* text) { *why = text; return rc; };
-    if (channels != 1 && channels != 3 && channels != 4) return no(BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
+    if (channels != 1 && channels != 3 && channels != 4 && !(two_ok && channels == 2)) return no(BLUR_ERR_INVALID, "channels must be 1, 3 or 4");
     if (!src || !dst || nframes < 0) return no(BLUR_ERR_INVALID, "null frame pointer or negative frame count");
     if (rows <= 0 || cols <= 0) return no(BLUR_ERR_INVALID, "rows and cols must be positive");
     if (!sigmas) return no(BLUR_ERR_INVALID, "sigmas must point to one sigma per frame");
@@ -2674,8 +2688,8 @@ static int fs_upload(blur_ctx* ctx, const std::vector<unsigned char>& host)
     return BLUR_OK;
 }
 
-// One driver over the element type, next to blur_ch_sigmas_batch_impl (u8 and float32 have entries; u16 and the half types would take
-// run_ff<T> as they do there).  Every distinct sigma gets the engine blur_ch_batch_impl's rules give it (the rules of choose_ch_engine;
+// One driver over the five element types, next to blur_ch_sigmas_batch_impl (u16 and the half types take run_ff<T> as they do there).
+// Every distinct sigma gets the engine blur_ch_batch_impl's rules give it (the rules of choose_ch_engine;
 // u8 with three channels: those of one and four channels, on fw_blur_u8<NKB, Q, 3> -- never the u8c3 entry, whatever the sigmas: a
 // frame's bytes depend on its pixels, its sigma and opts alone) and its fragments, taps and gains from mx_host_tables, the code
 // behind the scalar entries' cached tables; nothing goes into ctx->mx_tables.  All of that happens before the first launch.  Then, on
@@ -2683,17 +2697,20 @@ static int fs_upload(blur_ctx* ctx, const std::vector<unsigned char>& host)
 // table, and per window class the pre-pass and ONE fused launch over the class's frames (their list: FwFrame); the frames without
 // a fused kernel run one by one on the plane path.  The strips and sums workspaces are reused from class to class.
 // note: null for the call itself; the parts of a large in-place batch add to their caller's
+// two_ok (blur_nv_frame_sigmas_batch_impl: the interleaved Cb/Cr plane of an NV12 / P016 surface): channels = 2 is legal, u8 and u16 only.
+// plan_only: return once every sigma has its engine, before anything is written (that caller's check of one part ahead of the other's
+// launches)
 template <typename T>
 static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts,
-                                           const ChLayout* lay = nullptr, FramePlaneNote* note = nullptr, int frame0 = 0)
+                                           const ChLayout* lay = nullptr, FramePlaneNote* note = nullptr, int frame0 = 0, bool two_ok = false, bool plan_only = false)
 {
-    constexpr bool u8 = std::is_same_v<T, uint8_t>, ffk = !u8;
+    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;
     FrameSigmaPlan pl;
     if (lay)
-        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay, true)) return rc;
+        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay, true, two_ok)) return rc;
     {
         const char* why = nullptr;
-        if (int rc = frame_sigmas_status(d_src, d_dst, nframes, rows, cols, channels, sigmas, pl, &why)) return fail(ctx, rc, why);
+        if (int rc = frame_sigmas_status(d_src, d_dst, nframes, rows, cols, channels, sigmas, pl, &why, two_ok)) return fail(ctx, rc, why);
         if (!ctx) return BLUR_ERR_INVALID;
     }
     ChLayout L = lay ? *lay : ch_packed(rows, cols, channels, sizeof(T));
@@ -2708,6 +2725,11 @@ static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_d
     std::vector<MxHostTables> tabs(nslots);
     std::vector<const char*> why(nslots, nullptr);
     std::vector<char> fused(nslots, 0);
+    const std::string kind = std::string("fused kernel for ") + ch_type_name<T>() + " images: ";
+    const std::string no_class = kind + "pad 153 .. 168 has a kernel for 1 channel only";
+    const std::string no_contract = kind + (half ? "pad 105 .. 168 is outside the library's own choice, as for float32; ask for it with engine = FUSED"
+                                            : u16 ? "pad 105 .. 168 exceeds 1e-6 of full scale on full-scale content (1.2e-6); ask for it with engine = FUSED"
+                                                  : "pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED");
     for (int s = 0; s < nslots && choice != BLUR_ENGINE_FFT; ++s) {
         const FrameSigmaPlan::Slot& sl = pl.slots[s];
         const char* w = sl.nkb ? fx_frame_limits(rows, cols, quirk) : "fused matrix-core engine: no kernel instantiated for this pad";
@@ -2715,15 +2737,16 @@ static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_d
             std::vector<float> karr[2];
             if (mx_kernel_arrays(sl.sigma, sl.sz, nullptr, karr, &w) == BLUR_OK) (void)mx_host_tables(karr, sl.sz, sl.nkb, tabs[s], &w, false);
         }
-        if (!w && ffk && !ff_class_ok_t<T>(sl.nkb, channels)) w = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
-        else if (!w && ffk && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(sl.nkb))
-            w = "fused kernel for float32 images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED";
+        // (the texts of choose_ch_engine, by type)
+        if (!w && ffk && !ff_class_ok_t<T>(sl.nkb, channels)) w = no_class.c_str();
+        else if (!w && ffk && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(sl.nkb)) w = no_contract.c_str();
         else if (!w && std::max(ch_frame_span(rows, L.spitch, rowbytes), ch_frame_span(rows, L.dpitch, rowbytes)) > 0xfffff000ull)
             w = "fused matrix-core engine: frame too large for 32-bit offsets";
         if (w && choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, w);
         why[s] = w;
         fused[s] = w ? 0 : 1;
     }
+    if (plan_only) return BLUR_OK;
     if (!note) ctx->engine_note.clear();
     if (nframes == 0) return BLUR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2738,7 +2761,7 @@ static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_d
                 for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
                     const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
                     T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * L.dframe);
-                    if (int rc = blur_ch_frame_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas + f0, opts, lay, &pn, frame0 + f0)) return rc;
+                    if (int rc = blur_ch_frame_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas + f0, opts, lay, &pn, frame0 + f0, two_ok)) return rc;
                 }
                 nframes = 0;                                       // (the note is written below)
             }
@@ -2842,6 +2865,70 @@ static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_d
             ctx->engine_note = head + pn.why;
         }
     }
+    return BLUR_OK;
+}
+
+// ======================================================================================
+// One luma and one chroma sigma per frame of a decoded clip (blur_gaussian_{nv12,p016}_frame_sigmas_batch_dev): sigmas[2 f] and
+// sigmas[2 f + 1].  A call is a luma part (one channel) and a chroma part (two channels, two_ok) of blur_ch_frame_sigmas_batch_impl,
+// as blur_nv_batch_impl is two parts of blur_ch_sigmas_batch_impl.
+// ======================================================================================
+static int nv_frame_sigmas_status(const NvSurface& s, size_t es, int nframes, int rows, int cols, const double* sigmas, const char** why)
+{
+    auto no = [&](int rc, const char* text) { *why = text; return rc; };
+    if (int rc = nv_layout_status(s, es, nframes, rows, cols, sigmas, why)) return rc;
+    for (int i = 0; i < 2 * nframes; ++i)
+        if (!(sigmas[i] >= 0) || !std::isfinite(sigmas[i])) return no(BLUR_ERR_INVALID, "every sigma must be finite and positive, or 0 for a plane that is left as it is");
+    for (int i = 0; i < 2 * nframes; ++i) {
+        if (sigmas[i] == 0) continue;
+        const int r = (i & 1) ? rows / 2 : rows, c = (i & 1) ? cols / 2 : cols;
+        const Sizing sz = pffft_sizing(r, c, sigmas[i]);
+        if (sz.pad > r - 1 || sz.pad > c - 1)
+            return no(BLUR_ERR_UNSUPPORTED, (i & 1) ? "chroma pad > min(rows / 2, cols / 2) - 1 for one of the frames: reflect-101 would read outside the plane (chroma sigmas are in chroma pixels)"
+                                                    : "luma pad > min(rows, cols) - 1 for one of the frames: reflect-101 would read outside the plane");
+    }
+    return BLUR_OK;
+}
+
+template <typename T>
+static int blur_nv_frame_sigmas_batch_impl(blur_ctx* ctx, NvSurface s, int nframes, int rows, int cols, const double* sigmas, const blur_opts* opts)
+{
+    const char* why = nullptr;
+    if (int rc = nv_frame_sigmas_status(s, sizeof(T), nframes, rows, cols, sigmas, &why)) return fail(ctx, rc, why);
+    if (!ctx) return BLUR_ERR_INVALID;
+    if (nframes <= 1) s.sy_frame = s.suv_frame = s.dy_frame = s.duv_frame = 0;           // (a single frame's strides address nothing)
+    const ChLayout Ly{ s.spitch, s.sy_frame, s.dpitch, s.dy_frame }, Luv{ s.spitch, s.suv_frame, s.dpitch, s.duv_frame };
+    const int crows = rows / 2, ccols = cols / 2;
+    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
+    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, "NV12 / P016 surfaces: engine must be AUTO, FUSED or FFT");
+    std::vector<double> sy(nframes), sc(nframes);
+    bool blur_y = false, blur_c = false;
+    for (int f = 0; f < nframes; ++f) {
+        sy[f] = sigmas[2 * f];
+        sc[f] = sigmas[2 * f + 1];
+        blur_y = blur_y || sy[f] > 0;
+        blur_c = blur_c || sc[f] > 0;
+    }
+    const T* src_y = static_cast<const T*>(s.sy);
+    const T* src_uv = static_cast<const T*>(s.suv);
+    T* dst_y = static_cast<T*>(s.dy);
+    T* dst_uv = static_cast<T*>(s.duv);
+    // every chroma frame's engine before the luma part's first launch (the luma part chooses its own before it launches): a refused
+    // call has written nothing.  Only FUSED refuses.
+    if (choice == BLUR_ENGINE_FUSED)
+        if (int rc = blur_ch_frame_sigmas_batch_impl<T>(ctx, src_uv, dst_uv, nframes, crows, ccols, 2, sc.data(), opts, &Luv, nullptr, 0, true, true)) return rc;
+    if (nframes == 0) return BLUR_OK;
+    std::string note;
+    ctx->engine_note.clear();
+    if (int rc = blur_ch_frame_sigmas_batch_impl<T>(ctx, src_y, dst_y, nframes, rows, cols, 1, sy.data(), opts, &Ly)) return rc;
+    if (blur_y && !ctx->engine_note.empty()) note = "luma: " + ctx->engine_note;
+    ctx->engine_note.clear();
+    if (int rc = blur_ch_frame_sigmas_batch_impl<T>(ctx, src_uv, dst_uv, nframes, crows, ccols, 2, sc.data(), opts, &Luv, nullptr, 0, true)) return rc;
+    if (blur_c && !ctx->engine_note.empty()) note += (note.empty() ? "" : "; ") + std::string("chroma: ") + ctx->engine_note;
+    // family 6: every blurred plane of every frame ran on the fused kernel; 0: some took the plane path, and the note names them
+    ctx->last_family = note.empty() ? 6 : 0;
+    ctx->engine_note = note;
     return BLUR_OK;
 }
 
@@ -4523,6 +4610,61 @@ int blur_gaussian_f32_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const float*
 {
     const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
     return blur_ch_frame_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_u16_frame_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                    const blur_opts* opts)
+{
+    return blur_ch_frame_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_u16_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                    size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_frame_sigmas_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_f16_frame_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                    const blur_opts* opts)
+{
+    return blur_ch_frame_sigmas_batch_impl(ctx, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_f16_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                    size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_frame_sigmas_batch_impl(ctx, reinterpret_cast<const ff_f16*>(d_src), reinterpret_cast<ff_f16*>(d_dst), nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_bf16_frame_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                    const blur_opts* opts)
+{
+    return blur_ch_frame_sigmas_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigmas, opts);
+}
+
+int blur_gaussian_bf16_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst, size_t dst_pitch,
+                    size_t dst_frame_stride, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
+{
+    const ChLayout L{ src_pitch, src_frame_stride, dst_pitch, dst_frame_stride };
+    return blur_ch_frame_sigmas_batch_impl(ctx, reinterpret_cast<const ff_bf16*>(d_src), reinterpret_cast<ff_bf16*>(d_dst), nframes, rows, cols, channels, sigmas, opts, &L);
+}
+
+int blur_gaussian_nv12_frame_sigmas_batch_dev(blur_ctx* ctx, const uint8_t* d_src_y, const uint8_t* d_src_uv, size_t src_pitch, size_t src_y_frame_stride,
+                                              size_t src_uv_frame_stride, uint8_t* d_dst_y, uint8_t* d_dst_uv, size_t dst_pitch, size_t dst_y_frame_stride,
+                                              size_t dst_uv_frame_stride, int nframes, int rows, int cols, const double* sigmas, const blur_opts* opts)
+{
+    return blur_nv_frame_sigmas_batch_impl<uint8_t>(ctx, NvSurface{ d_src_y, d_src_uv, d_dst_y, d_dst_uv, src_pitch, src_y_frame_stride, src_uv_frame_stride, dst_pitch,
+                                                    dst_y_frame_stride, dst_uv_frame_stride }, nframes, rows, cols, sigmas, opts);
+}
+
+int blur_gaussian_p016_frame_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src_y, const uint16_t* d_src_uv, size_t src_pitch, size_t src_y_frame_stride,
+                                              size_t src_uv_frame_stride, uint16_t* d_dst_y, uint16_t* d_dst_uv, size_t dst_pitch, size_t dst_y_frame_stride,
+                                              size_t dst_uv_frame_stride, int nframes, int rows, int cols, const double* sigmas, const blur_opts* opts)
+{
+    return blur_nv_frame_sigmas_batch_impl<uint16_t>(ctx, NvSurface{ d_src_y, d_src_uv, d_dst_y, d_dst_uv, src_pitch, src_y_frame_stride, src_uv_frame_stride, dst_pitch,
+                                                    dst_y_frame_stride, dst_uv_frame_stride }, nframes, rows, cols, sigmas, opts);
 }
 
 // host-only: how a call with these sigmas groups its frames

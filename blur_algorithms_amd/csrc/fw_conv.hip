@@ -1,7 +1,7 @@
 // The fused matrix-core kernel with one channel per workgroup (fw_kernels.hpp), one window class per compilation:
 // -DBLUR_INST_NKB=<NKB> -> build/fw_conv_<NKB>.o.  Every class: one, two and four channels (FcEntry; two: the chroma plane of an NV12
-// surface, without the frame-list variants), and three channels for the launches over a subset of them (Fw3Entry: one sigma per
-// channel).  NKB >= 13 as well: whole BGR frames (FxEntry, pad 73 .. 168).
+// surface), and three channels for the launches over a subset of them (Fw3Entry: one sigma per channel), each with and without a
+// frame list.  NKB >= 13 as well: whole BGR frames (FxEntry, pad 73 .. 168).
 #include "fw_kernels.hpp"
 #include "fx_registry.hpp"
 namespace blur_amd {

@@ -593,27 +593,6 @@ template <int NKB, int CH> hipError_t fw_launch(hipStream_t st, const uint8_t* s
     return hipGetLastError();
 }
 
-// two channels: fw_launch without the instantiations for a frame list (no entry with one sigma per frame takes two channels)
-template <int NKB> hipError_t fw_launch2(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FcQuirk* qk,
-                                         const uint8_t* strips, FwChSel chsel, FwPitch pt)
-{
-    using C = FwCfg<NKB>;
-    const int nact = fw_chsel_count(chsel);
-    if (nact < 1 || nact > 2) return hipErrorInvalidValue;
-    for (int i = 0; i < nact; ++i)
-        if (static_cast<int>((chsel >> (4 + 2 * i)) & 3u) >= 2) return hipErrorInvalidValue;
-    const FxLaunch l = fx_plan_launch(g, nact, C::NT, num_cus);
-    if (l.ntasks == 0) return hipSuccess;
-    static std::atomic<unsigned long long> attr_done{ 0 };
-    const hipError_t e = fx_set_lds(attr_done, C::LDS, fw_blur_u8<NKB, true, 2>, fw_blur_u8<NKB, false, 2>);
-    if (e != hipSuccess) return e;
-    const mx_half8* fr = static_cast<const mx_half8*>(frags);
-    const int nt = static_cast<int>(l.ntasks);
-    if (qk) hipLaunchKernelGGL((fw_blur_u8<NKB, true, 2>), l.grid, dim3(256), C::LDS, st, src, dst, fr, g, l.chunks, l.tps, l.nseg, nt, *qk, strips, chsel, pt, FwNoFrames{});
-    else hipLaunchKernelGGL((fw_blur_u8<NKB, false, 2>), l.grid, dim3(256), C::LDS, st, src, dst, fr, g, l.chunks, l.tps, l.nseg, nt, FcQuirk{}, strips, chsel, pt, FwNoFrames{});
-    return hipGetLastError();
-}
-
 // the three-channel entry (FxEntry; fx_registry.hpp: find_entry_for_pad) of the wide windows
 template <int NKB> hipError_t fw_launch_u8c3(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int num_cus, const FxQuirk* qk,
                                              const uint8_t* strips, float* vdump, unsigned long long* stamps)
@@ -644,13 +623,13 @@ template <int NKB> hipError_t fw_launch_u8c3_sel(hipStream_t st, const uint8_t* 
 }
 
 // the one-, two- and four-channel entry (FcEntry; fx_registry.hpp: find_entry) of every window class (two channels: the chroma plane
-// of an NV12 surface -- blur_gaussian_nv12_*; no public entry takes channels = 2)
+// of an NV12 surface -- blur_gaussian_nv12_*, with a frame list blur_gaussian_nv12_frame_sigmas_*; no public entry takes channels = 2)
 template <int NKB> hipError_t fw_launch_u8c14(hipStream_t st, const uint8_t* src, uint8_t* dst, const void* frags, FxGeom g, int ch, int num_cus, const FcQuirk* qk,
                                               const uint8_t* strips, FwChSel chsel, FwPitch pt, const FwFrame* ft)
 {
     if (ch == 1) return fw_launch<NKB, 1>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
     if (ch == 4) return fw_launch<NKB, 4>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
-    if (ch == 2) return ft ? hipErrorInvalidValue : fw_launch2<NKB>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt);
+    if (ch == 2) return fw_launch<NKB, 2>(st, src, dst, frags, g, num_cus, qk, strips, chsel, pt, ft);
     return hipErrorInvalidValue;
 }
 
@@ -817,6 +796,11 @@ __global__ __launch_bounds__(256) void fc_prepass_frames(const uint8_t* __restri
         fc_edge_strips_body<CH>(s, strips, rows, cols, pada, chunks, nright, bx, sidx, f, spitch, sframe);
     }
 }
+
+// fc_prepass_frames<2, G> on `nblocks` workgroups (G = 1, 2, 4): instantiated and launched in fc_frames2.hip, which says why
+hipError_t fc_prepass_frames2_launch(int G, unsigned nblocks, hipStream_t st, const uint8_t* src, int* srow, int* cpart, long long* zsum, uint8_t* strips, int rows, int cols,
+                                     int pada, int nbands, int nbatches, int cpitch, int n_alt, int chunks, int nright, int strip_blocks, int band_rows, unsigned chmask,
+                                     uint32_t spitch, size_t sframe, const FwFrame* ft);
 
 #ifdef BLUR_FX_QUIRK_KERNELS
 // fx_prepass (three channels: fx_kernels.hpp) for a launch over frames with their own sigmas, as fc_prepass_frames

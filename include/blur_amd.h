@@ -584,9 +584,11 @@ int blur_gaussian_sigmas_plan(int rows, int cols, int channels, const double* si
 /* ---- one sigma per frame, DEVICE pointers -------------------------------------------------------------------------------------
    The _frame_sigmas_ entries take `const double sigmas[nframes]` (HOST memory) where the batch entries take `double sigma`: an
    augmentation that draws a sigma per image of a training batch, a clip whose blur changes from frame to frame, or (pitched entry,
-   src_frame_stride = 0) one frame blurred with K sigmas into K outputs.  u8 and float32, channels in {1, 3, 4}.
+   src_frame_stride = 0) one frame blurred with K sigmas into K outputs.  u8, float32, u16, float16 and bfloat16 (the 16-bit types as
+   uint16_t samples, as in their scalar entries), channels in {1, 3, 4}; decoded NV12 / P016 clips have entries of their own below.
      sigmas[f] > 0   frame f of the result is, bit for bit, what the scalar entry of the same type returns for that frame alone with
-                     sigma = sigmas[f] and the same opts (a float32 frame's power-of-two scale comes from its own max|x|).  The one
+                     sigma = sigmas[f] and the same opts (a float32, float16 or bfloat16 frame's power-of-two scale comes from its own
+                     max|x|).  The one
                      exception is u8 with three channels, where the scalar call runs its own three-channel kernels: such a frame
                      runs on the one-channel-per-workgroup kernel (the route of the _sigmas_ and pitched entries) and meets the same
                      float64 oracle under the same tie rule.  Three-channel u8 frames are NEVER forwarded to the u8c3 entry, not even
@@ -599,7 +601,8 @@ int blur_gaussian_sigmas_plan(int rows, int cols, int channels, const double* si
    scalar entry has one per frame.  The fragments and taps of the call's sigmas are built on the host and uploaded once per call
    into a workspace of the context; nothing is cached per sigma, so a stream of never-repeating sigmas costs no device memory.
    opts->engine applies per frame: AUTO gives a frame the fused kernel wherever the scalar entry's rules give it to that sigma (u8
-   with three channels: wherever the 1- and 4-channel rules do) and the f32 plane path elsewhere, one frame at a time; FUSED fails
+   with three channels: wherever the 1- and 4-channel rules do; float32, u16 and the half types: pad <= 104) and the f32 plane path
+   elsewhere, one frame at a time; FUSED fails
    with BLUR_ERR_UNSUPPORTED, before anything is written, if any frame has no fused kernel; FFT takes the plane path for every
    frame.  After the call blur_last_engine returns family 6 if every blurred frame ran on the fused kernel and 0 otherwise; the note
    then says how many frames took the plane path and names the first of them, its sigma and the reason.
@@ -622,7 +625,45 @@ int blur_gaussian_u8_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint8_t
 int blur_gaussian_f32_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const float* d_src, size_t src_pitch, size_t src_frame_stride, float* d_dst,
                                                      size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
                                                      const double* sigmas, const blur_opts* opts);
-/* host-only plan of the calls above (no GPU needed; the same host code the entries use): for frame f, out[4 f] = its launch group
+int blur_gaussian_u16_frame_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                             const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f16_frame_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                             const double* sigmas, const blur_opts* opts);
+int blur_gaussian_bf16_frame_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels,
+                                              const double* sigmas, const blur_opts* opts);
+int blur_gaussian_u16_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                                     size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                                     const double* sigmas, const blur_opts* opts);
+int blur_gaussian_f16_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                                     size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                                     const double* sigmas, const blur_opts* opts);
+int blur_gaussian_bf16_frame_sigmas_pitched_batch_dev(blur_ctx* ctx, const uint16_t* d_src, size_t src_pitch, size_t src_frame_stride, uint16_t* d_dst,
+                                                      size_t dst_pitch, size_t dst_frame_stride, int nframes, int rows, int cols, int channels,
+                                                      const double* sigmas, const blur_opts* opts);
+/* A decoded clip whose blur changes from frame to frame (a focus pull, a blur ramp): the arguments of blur_gaussian_{nv12,p016}_batch_dev
+   with `const double sigmas[2 * nframes]` (HOST memory): sigmas[2 f] is frame f's luma sigma, sigmas[2 f + 1] the sigma of both of
+   its chroma channels, each in pixels of its own plane (separate Cb and Cr sigmas per frame: the scalar entry, frame by frame).
+     result   the planes of frame f are, bit for bit, what blur_gaussian_{nv12,p016}_dev returns for that frame alone with
+              (sigmas[2 f], sigmas[2 f + 1], sigmas[2 f + 1]) and the same opts.
+     zero     a sigma of 0 leaves that plane of that frame as it is: copied out of place, untouched in place.
+     writes, overlap   as the scalar surface entries, per plane.
+     cost     the luma planes and the chroma planes are each one call of the driver behind the entries above: per window class one
+              pre-pass and one fused launch over the class's frames (the chroma plane on the two-channel kernels).
+     engine   per plane and per frame, the scalar surface entry's rules; the engine of every plane of every frame is chosen before
+              the first launch, so a FUSED refusal has written nothing.  blur_last_engine: 6 if every blurred plane of every frame
+              ran fused, else 0 with a note that names the luma and / or chroma frames on the plane path.
+   Status: the scalar surface entries' checks in their order, with both sigmas of every frame checked (finite, >= 0), then
+   BLUR_ERR_UNSUPPORTED where any frame's luma pad exceeds min(rows, cols) - 1 or its chroma pad min(rows / 2, cols / 2) - 1; all
+   before the device is touched (ctx may then be NULL). */
+int blur_gaussian_nv12_frame_sigmas_batch_dev(blur_ctx* ctx, const uint8_t* d_src_y, const uint8_t* d_src_uv, size_t src_pitch, size_t src_y_frame_stride,
+                                              size_t src_uv_frame_stride, uint8_t* d_dst_y, uint8_t* d_dst_uv, size_t dst_pitch,
+                                              size_t dst_y_frame_stride, size_t dst_uv_frame_stride, int nframes, int rows, int cols,
+                                              const double* sigmas, const blur_opts* opts);
+int blur_gaussian_p016_frame_sigmas_batch_dev(blur_ctx* ctx, const uint16_t* d_src_y, const uint16_t* d_src_uv, size_t src_pitch, size_t src_y_frame_stride,
+                                              size_t src_uv_frame_stride, uint16_t* d_dst_y, uint16_t* d_dst_uv, size_t dst_pitch,
+                                              size_t dst_y_frame_stride, size_t dst_uv_frame_stride, int nframes, int rows, int cols,
+                                              const double* sigmas, const blur_opts* opts);
+/* host-only plan of the _frame_sigmas_ entries of one pixel type (no GPU needed; the same host code the entries use): for frame f, out[4 f] = its launch group
    (the frames of one window class share an index, counted in the order of their first frame; -1 for sigma = 0), out[4 f + 1] = the
    pad of its sigma, out[4 f + 2] = the fused kernel's window class NKB, 8 (NKB - 4) < pad <= 8 (NKB - 2), or 0 where the pad has no
    fused kernel (pad > 168; these frames form a group of their own), out[4 f + 3] = its table slot (frames of equal sigma share

@@ -366,6 +366,45 @@ inline void gaussian_blur_p016_dev(const uint16_t* d_src_y, const uint16_t* d_sr
     if (!ctx) ctx = default_ctx();
     check(ctx, blur_gaussian_p016_dev(ctx, d_src_y, d_src_uv, src_step, d_dst_y, d_dst_uv, dst_step, rows, cols, sigmas, opts), "gaussian_blur_p016_dev");
 }
+// A decoded clip of nframes surfaces with its own sigmas per frame (blur_amd.h: blur_gaussian_nv12_frame_sigmas_batch_dev): the planes
+// of frame f lie f * *_y_frame_step and f * *_uv_frame_step bytes behind the first frame's; sigmas[2 f] is frame f's luma sigma,
+// sigmas[2 f + 1] the sigma of both of its chroma channels, each in pixels of its own plane; 0 leaves that plane of that frame as it is.
+inline void gaussian_blur_nv12_per_frame_dev(const uint8_t* d_src_y, const uint8_t* d_src_uv, size_t src_step, size_t src_y_frame_step, size_t src_uv_frame_step,
+                                             uint8_t* d_dst_y, uint8_t* d_dst_uv, size_t dst_step, size_t dst_y_frame_step, size_t dst_uv_frame_step, int nframes,
+                                             int rows, int cols, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_nv12_frame_sigmas_batch_dev(ctx, d_src_y, d_src_uv, src_step, src_y_frame_step, src_uv_frame_step, d_dst_y, d_dst_uv, dst_step,
+                                                         dst_y_frame_step, dst_uv_frame_step, nframes, rows, cols, sigmas, opts), "gaussian_blur_nv12_per_frame_dev");
+}
+inline void gaussian_blur_p016_per_frame_dev(const uint16_t* d_src_y, const uint16_t* d_src_uv, size_t src_step, size_t src_y_frame_step, size_t src_uv_frame_step,
+                                             uint16_t* d_dst_y, uint16_t* d_dst_uv, size_t dst_step, size_t dst_y_frame_step, size_t dst_uv_frame_step, int nframes,
+                                             int rows, int cols, const double* sigmas, blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_p016_frame_sigmas_batch_dev(ctx, d_src_y, d_src_uv, src_step, src_y_frame_step, src_uv_frame_step, d_dst_y, d_dst_uv, dst_step,
+                                                         dst_y_frame_step, dst_uv_frame_step, nframes, rows, cols, sigmas, opts), "gaussian_blur_p016_per_frame_dev");
+}
+// nframes packed frames [rows, cols, channels] of uint16, float16 or bfloat16 samples (16-bit patterns) with sigmas[f] for frame f; 0
+// copies the frame (blur_amd.h: blur_gaussian_u16_frame_sigmas_batch_dev).  The destination may be the source.
+inline void gaussian_blur_u16_per_frame_dev(const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                            blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_u16_frame_sigmas_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts), "gaussian_blur_u16_per_frame_dev");
+}
+inline void gaussian_blur_f16_per_frame_dev(const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                            blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_f16_frame_sigmas_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts), "gaussian_blur_f16_per_frame_dev");
+}
+inline void gaussian_blur_bf16_per_frame_dev(const uint16_t* d_src, uint16_t* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas,
+                                             blur_ctx* ctx = nullptr, const blur_opts* opts = nullptr)
+{
+    if (!ctx) ctx = default_ctx();
+    check(ctx, blur_gaussian_bf16_frame_sigmas_batch_dev(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, opts), "gaussian_blur_bf16_per_frame_dev");
+}
 
 // pocketfft_1D(image, sigma) (Source.cpp:280-392) and pocketfft_2D(image, sigma) (Source.cpp:143-277): the two
 // pocketfft paths multiply all N/2+1 bins with the kernel's own spectrum (no Nyquist-slot quirk) and, inside the

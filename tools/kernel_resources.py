@@ -10,7 +10,12 @@
     tools/kernel_resources.py --same-code BASE NEW        whether two builds hold the same device code: per object (directories are
                                                           matched by basename), the same kernel names and the same sha256 of the
                                                           code object's .text (not of the whole code object: its metadata names the
-                                                          source file).  Exit status 1 on any difference or unmatched object
+                                                          source file).  Where the builds hold different kernels (one of them
+                                                          added instantiations to an object), the kernels present in both are
+                                                          compared one by one, by the sha256 of each kernel's own bytes of .text,
+                                                          and the others are listed, as is an object that only NEW has (new
+                                                          kernels only).  Exit status 1 on a kernel or an object that differs, or
+                                                          an object that only BASE has
 """
 import glob
 import hashlib
@@ -26,7 +31,8 @@ FIELDS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sg
 
 def kernels(obj, arch="gfx950", text=False):
     """{kernel name: (vgpr, agpr, sgpr, vgpr spills, sgpr spills, scratch bytes)} of one host object with an embedded code object;
-    with text, the sha256 of the code object's .text as well: (kernels, digest)"""
+    with text, the sha256 of the code object's .text and {kernel name: sha256 of its own bytes of .text} as well: (kernels, digest,
+    per kernel)"""
     with tempfile.TemporaryDirectory() as tmp:
         fb, co = os.path.join(tmp, "a.hipfb"), os.path.join(tmp, "a.co")
         subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(tmp, "copy.o")])
@@ -36,7 +42,16 @@ def kernels(obj, arch="gfx950", text=False):
         if text:
             subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.text", co, os.path.join(tmp, "a.text")])
             with open(os.path.join(tmp, "a.text"), "rb") as f:
-                digest = hashlib.sha256(f.read()).hexdigest()
+                code = f.read()
+            digest = hashlib.sha256(code).hexdigest()
+            sections = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "-S", "-W", co], text=True)
+            base = int(re.search(r"\s\.text\s+PROGBITS\s+([0-9a-f]+)", sections).group(1), 16)
+            per = {}
+            for line in subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "-s", "-W", co], text=True).splitlines():
+                f = line.split()
+                if len(f) == 8 and f[3] == "FUNC" and f[6] != "UND":
+                    at, size = int(f[1], 16) - base, int(f[2], 0)
+                    per[f[7]] = hashlib.sha256(code[at:at + size]).hexdigest()
     out = {}
     for block in re.split(r"\n\s*- \.agpr_count:", "\n" + notes)[1:]:
         block = "    - .agpr_count:" + block
@@ -48,7 +63,7 @@ def kernels(obj, arch="gfx950", text=False):
             m = re.search(re.escape(f) + r":\s+(\d+)", block)
             vals.append(int(m.group(1)) if m else 0)
         out[name.group(1)] = tuple(vals)
-    return (out, digest) if text else out
+    return (out, digest, per) if text else out
 
 
 def objects(path):
@@ -65,19 +80,27 @@ def same_code(base, new):
     for name in sorted(set(bo) | set(no)):
         if name not in bo or name not in no:
             print("unmatched object", name, "(only in %s)" % (new if name in no else base))
-            bad += 1
+            bad += name in bo
             continue
         try:
-            (kb, tb), (kn, tn) = kernels(bo[name], text=True), kernels(no[name], text=True)
+            (kb, tb, pb), (kn, tn, pn) = kernels(bo[name], text=True), kernels(no[name], text=True)
         except subprocess.CalledProcessError:
             continue                                      # no device code in this object
         nobj += 1
         nker += len(kn)
+        if set(kb) == set(kn):
+            if tb != tn:
+                print("differs", name, ".text", tb[:16], "->", tn[:16])
+                bad += 1
+            continue
+        # other kernels in one build: those of both, one by one
         for k in sorted(set(kb) ^ set(kn)):
-            print("unmatched kernel", name, k)
-        if set(kb) != set(kn) or tb != tn:
-            print("differs", name, ".text", tb[:16], "->", tn[:16])
-            bad += 1
+            print("only in", "NEW " if k in kn else "BASE", name, k)
+        changed = [k for k in sorted(set(kb) & set(kn)) if k not in pb or k not in pn or pb[k] != pn[k]]
+        for k in changed:
+            print("differs", name, k)
+        print("%s: %d kernels of both builds compared one by one, %d differ" % (name, len(set(kb) & set(kn)), len(changed)))
+        bad += 1 if changed else 0
     print("%d objects with device code compared (%d kernels), %d differ or are unmatched" % (nobj, nker, bad))
     return 1 if bad else 0
 
