@@ -1783,7 +1783,7 @@ static ChLayout ch_packed(int rows, int cols, int ch, size_t es)
 }
 // the bytes from a frame's first to behind its last
 static size_t ch_frame_span(int rows, size_t pitch, size_t rowbytes) { return static_cast<size_t>(rows - 1) * pitch + rowbytes; }
-// the fused kernels' view of a layout (choose_ch_engine has checked that a frame's span fits 32-bit offsets)
+// the fused kernels' view of a layout (ch_fused_refusal has checked that a frame's span fits 32-bit offsets)
 static FwPitch fw_pitch_of(const ChLayout& L)
 {
     return FwPitch{ static_cast<uint32_t>(L.spitch), static_cast<uint32_t>(L.dpitch), L.sframe, L.dframe };
@@ -2131,19 +2131,22 @@ static bool ch_spans_overlap(const void* src, const void* dst, int nframes, int 
     return s0 < d0 + dspan && d0 < s0 + sspan;
 }
 
-// the source rectangles -> ctx->ch_copy, packed; *src and the layout's source side then describe the copy
+// Where the spans of the nframes source and destination frames overlap (the fused kernel reads its neighbours' pixels while it
+// writes, and the plane path writes frame f before it reads frame f + 1): the first ncopy source rectangles -> ctx->ch_copy, packed;
+// *src and the layout's source side then describe the copy
 template <typename T>
-static int ch_copy_source(blur_ctx* ctx, const T** src, int nframes, int rows, size_t rowbytes, ChLayout& L)
+static int ch_copy_source(blur_ctx* ctx, const T** src, const T* dst, int nframes, int ncopy, int rows, size_t rowbytes, ChLayout& L)
 {
+    if (!ch_spans_overlap(*src, dst, nframes, rows, rowbytes, L)) return BLUR_OK;
     const size_t fb = rowbytes * rows;
-    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * nframes)) return rc;
-    if (L.spitch == rowbytes && (nframes == 1 || L.sframe == fb)) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, *src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (int rc = ensure_buf(ctx, reinterpret_cast<void**>(&ctx->ch_copy), &ctx->ch_copy_bytes, fb * ncopy)) return rc;
+    if (L.spitch == rowbytes && (ncopy == 1 || L.sframe == fb)) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ch_copy, *src, fb * ncopy, hipMemcpyDeviceToDevice, ctx->stream));
     } else {
         const uintptr_t bits = reinterpret_cast<uintptr_t>(*src) | L.spitch | L.sframe | rowbytes | reinterpret_cast<uintptr_t>(ctx->ch_copy);
         const size_t vb = (bits & 15) == 0 ? 16 : ((bits & 3) == 0 ? 4 : 1);
         const unsigned bx = static_cast<unsigned>(std::min<size_t>((rowbytes / vb + 255) / 256, 64));
-        const dim3 grid(bx, static_cast<unsigned>(std::min<size_t>(rows, 1024)), static_cast<unsigned>(nframes));
+        const dim3 grid(bx, static_cast<unsigned>(std::min<size_t>(rows, 1024)), static_cast<unsigned>(ncopy));
         auto kern = vb == 16 ? ch_gather_rows<uint4> : (vb == 4 ? ch_gather_rows<uint32_t> : ch_gather_rows<unsigned char>);
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const unsigned char*>(*src), reinterpret_cast<unsigned char*>(ctx->ch_copy), rows,
                            rowbytes, L.spitch, L.sframe);
@@ -2155,40 +2158,99 @@ static int ch_copy_source(blur_ctx* ctx, const T** src, int nframes, int rows, s
     return BLUR_OK;
 }
 
+// a call that writes its frames where it reads them
+static bool ch_in_place(const void* src, const void* dst, const ChLayout& L) { return src == dst && L.spitch == L.dpitch && L.sframe == L.dframe; }
+
+// An in-place batch that reads from a copy runs in parts of at most 1 GiB (a part's result never touches a later part's source).
+// True where the batch is larger than that: body(part, nf, f0) has run on the nf frames from frame f0 on, and *rc is its status
+template <typename T, typename Body>
+static bool ch_in_place_parts(T* d_dst, int nframes, size_t fb, size_t dframe, int* rc, Body body)
+{
+    const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
+    if (static_cast<size_t>(nframes) <= cap) return false;
+    *rc = BLUR_OK;
+    for (int f0 = 0; f0 < nframes && *rc == BLUR_OK; f0 += static_cast<int>(cap)) {
+        const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
+        T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * dframe);
+        *rc = body(part, nf, f0);
+    }
+    return true;
+}
+
+// opts (null: the defaults) with another engine
+static blur_opts with_engine(const blur_opts* opts, int engine)
+{
+    blur_opts o;
+    if (opts) o = *opts;
+    else blur_opts_default(&o);
+    o.engine = engine;
+    return o;
+}
+
+// The engine a per-channel call asks for (opts null: AUTO).  The fused kernel and the plane path are all these entries have: -1 for
+// any other engine, with the call's error set (BLUR_ERR_UNSUPPORTED)
+static int ch_engine_choice(blur_ctx* ctx, const blur_opts* opts, const char* who, const char* what)
+{
+    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
+    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
+        return fail(ctx, BLUR_ERR_UNSUPPORTED, (std::string(who) + what + ": engine must be AUTO, FUSED or FFT").c_str()), -1;
+    return choice;
+}
+
+// What takes the fused kernel of window class nkb away from pixel type T (empty: nothing does).  float32 has no kernel for NKB 23
+// with 3 or 4 channels (ff_class_ok_t); the own choice of float32 and u16 stops at NKB 15 (ff_class_in_contract: at 16 bits 1e-6 of
+// full scale is 0.066 of a grey level); the 32-bit offsets limit the frame's bytes (a pitched frame: its span, (rows - 1) pitch + a
+// row's bytes).  own_name: the one-sigma-per-frame driver's wording, which names T where choose_ch_engine's says "float16 /
+// bfloat16" of both half types
+template <typename T>
+static std::string ch_fused_refusal(int nkb, int rows, int cols, int channels, int choice, const ChLayout& L, bool own_name)
+{
+    constexpr bool u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !std::is_same_v<T, uint8_t>;      // ffk: the ff_kernels.hpp types
+    const size_t rowbytes = static_cast<size_t>(cols) * channels * sizeof(T);
+    const std::string fused = "fused kernel for ";
+    if (ffk && !ff_class_ok_t<T>(nkb, channels)) return fused + ch_type_name<T>() + " images: pad 153 .. 168 has a kernel for 1 channel only";
+    if (ffk && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(nkb))
+        return fused + (half && !own_name ? "float16 / bfloat16" : ch_type_name<T>()) +
+               (half ? " images: pad 105 .. 168 is outside the library's own choice, as for float32; ask for it with engine = FUSED"
+                : u16 ? " images: pad 105 .. 168 exceeds 1e-6 of full scale on full-scale content (1.2e-6); ask for it with engine = FUSED"
+                      : " images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED");
+    if (std::max(ch_frame_span(rows, L.spitch, rowbytes), ch_frame_span(rows, L.dpitch, rowbytes)) > 0xfffff000ull)
+        return "fused matrix-core engine: frame too large for 32-bit offsets";
+    return std::string();
+}
+
+// the fused kernel of the pixel type over the channels in chsel (frames: the list of a launch over frames with their own sigmas)
+template <typename T>
+static int run_ch_fused(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const Prepared& p, FwChSel chsel, const ChLayout& L,
+                        const FwFrame* frames = nullptr)
+{
+    if constexpr (!std::is_same_v<T, uint8_t>) return run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p, chsel, L, frames);
+    else return channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, nframes, rows, cols, p, nullptr, chsel, &L, frames)
+                              : run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p, chsel, L, frames);
+}
+
 // The engine of a per-channel blur with one sigma (blur_ch_batch_impl; blur_ch_sigmas_batch_impl: of a group of channels): p.fx set =
 // the fused kernel, else the plane fallback, and `note` says why.  choice: AUTO, FUSED or FFT.
 template <typename T>
 static int choose_ch_engine(blur_ctx* ctx, int rows, int cols, int channels, double sigma, const blur_opts* opts, int choice, Prepared& p, std::string& note,
                             const ChLayout& L)
 {
-    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;
     // The fused kernel wherever it applies (prepare's rules for BLUR_ENGINE_FUSED: a kernel for the pad, the frame and quirk limits; a
     // float32 class instantiated for the channel count; the frame's bytes within 32-bit offsets), the plane fallback elsewhere.  AUTO
     // too: where the u8c3 policy passes the fused engine over for a compile-time FFT family (frames under 1 MP, pad > 152 on 6 MP), the
     // alternative here is the run-time-planned plane path, three to four times slower than the fused kernel (4K sigma 50, 8 frames:
     // 0.146 ms per 1-channel u8 frame, 0.568 per 4-channel one, on the plane path)
     if (choice != BLUR_ENGINE_FFT) {
-        blur_opts fo;
-        blur_opts_default(&fo);
-        if (opts) fo = *opts;
-        fo.engine = BLUR_ENGINE_FUSED;
+        const blur_opts fo = with_engine(opts, BLUR_ENGINE_FUSED);
         const int rc = prepare(ctx, rows, cols, sigma, &fo, p, true);
         if (rc == BLUR_ERR_UNSUPPORTED && choice == BLUR_ENGINE_AUTO) {
             p = Prepared{};
             note = ctx->err;
             ctx->err.clear();                    // (not a failure of this call)
         } else if (rc) return rc;
-        const char* why = nullptr;
-        if (p.fx && ffk && !ff_class_ok_t<T>(p.fx->nkb, channels)) why = "fused kernel for float32 images: pad 153 .. 168 has a kernel for 1 channel only";
-        else if (p.fx && ffk && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(p.fx->nkb))
-            why = half ? "fused kernel for float16 / bfloat16 images: pad 105 .. 168 is outside the library's own choice, as for float32; ask for it with engine = FUSED"
-                  : u16 ? "fused kernel for u16 images: pad 105 .. 168 exceeds 1e-6 of full scale on full-scale content (1.2e-6); ask for it with engine = FUSED"
-                      : "fused kernel for float32 images: pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED";
-        else if (p.fx && std::max(ch_frame_span(rows, L.spitch, static_cast<size_t>(cols) * channels * sizeof(T)),
-                                  ch_frame_span(rows, L.dpitch, static_cast<size_t>(cols) * channels * sizeof(T))) > 0xfffff000ull)
-            why = "fused matrix-core engine: frame too large for 32-bit offsets";       // (a pitched frame: its span, (rows - 1) pitch + a row's bytes)
-        if (why) {
-            if (choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, why);
+        const std::string why = p.fx ? ch_fused_refusal<T>(p.fx->nkb, rows, cols, channels, choice, L, false) : std::string();
+        if (!why.empty()) {
+            if (choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, why.c_str());
             p.fx = nullptr;
             note = why;
         }
@@ -2196,15 +2258,13 @@ static int choose_ch_engine(blur_ctx* ctx, int rows, int cols, int channels, dou
     return BLUR_OK;
 }
 
-// One driver for the five element types (float16 and bfloat16: in everything below as float32, two bytes per sample).  What differs by type: u8 forwards 3 channels to the u8c3 entry; float32 has no fused
-// kernel for NKB 23 with 3 or 4 channels (ff_class_ok_t); the own choice of float32 and u16 stops at NKB 15 (ff_class_in_contract: at 16 bits
-// 1e-6 of full scale is 0.066 of a grey level); the 32-bit offsets limit the frame's bytes; the fused kernel (run_fc_u8 / run_ff<T>)
-// and the engine error's text
+// One driver for the five element types (float16 and bfloat16: in everything below as float32, two bytes per sample).  What differs by type: u8 forwards 3 channels to the u8c3 entry;
+// the rules that take the fused kernel away (ch_fused_refusal); the fused kernel (run_ch_fused) and the engine error's text
 template <typename T>
 static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts,
                               const ChLayout* lay = nullptr)
 {
-    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;      // ffk: the ff_kernels.hpp types
+    constexpr bool u8 = std::is_same_v<T, uint8_t>;
     // lay: the pitched entries' layout (null: packed frames).  Three u8 channels, packed: the u8c3 entry and its kernels; pitched:
     // fw_blur_u8<NKB, Q, 3> over the three channels (Fw3Entry), the route of the one-sigma-per-channel calls
     if (lay)
@@ -2215,67 +2275,61 @@ static int blur_ch_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nfram
     }
     ChLayout L = lay ? *lay : ch_packed(rows, cols, channels, sizeof(T));
     if (nframes == 1) L.sframe = L.dframe = 0;               // (not used; in-place calls compare the layouts)
-    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
-    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, half ? (std::string(ch_type_name<T>()) + " images: engine must be AUTO, FUSED or FFT").c_str()
-                                                    : (u16 ? "u16 images: engine must be AUTO, FUSED or FFT"
-                                                           : (ffk ? "float32 images: engine must be AUTO, FUSED or FFT" : "1- and 4-channel images: engine must be AUTO, FUSED or FFT")));
+    const int choice = ch_engine_choice(ctx, opts, u8 ? "1- and 4-channel" : ch_type_name<T>(), " images");
+    if (choice < 0) return BLUR_ERR_UNSUPPORTED;
     Prepared p;
     std::string note;
     if (int rc = choose_ch_engine<T>(ctx, rows, cols, channels, sigma, opts, choice, p, note, L)) return rc;
     if (nframes == 0) return BLUR_OK;
     const size_t rowbytes = static_cast<size_t>(cols) * channels * sizeof(T), fb = rowbytes * rows;
-    // overlap of the source and destination spans (over the whole batch; pitched frames: ch_spans_overlap): the fused kernel reads
-    // its neighbours' pixels while it writes, and the plane path writes frame f before it reads frame f + 1.  An in-place call of
-    // the plane path needs no copy (frame f is read whole before it is written); every other overlap reads from a copy
-    const bool in_place = d_src == d_dst && L.spitch == L.dpitch && L.sframe == L.dframe;
-    if (ch_spans_overlap(d_src, d_dst, nframes, rows, rowbytes, L) && (p.fx || !in_place)) {
-        if (in_place) {             // in parts of at most 1 GiB (a part's result never touches a later part's source)
-            const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
-            if (static_cast<size_t>(nframes) > cap) {
-                for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
-                    const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
-                    T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * L.dframe);
-                    if (int rc = blur_ch_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts, lay)) return rc;
-                }
-                return BLUR_OK;
-            }
-        }
-        if (int rc = ch_copy_source(ctx, &d_src, nframes, rows, rowbytes, L)) return rc;
+    // an in-place call of the plane path needs no copy (frame f is read whole before it is written); every other overlap reads from one
+    const bool in_place = ch_in_place(d_src, d_dst, L);
+    if (p.fx || !in_place) {
+        int rc;
+        if (in_place && ch_in_place_parts(d_dst, nframes, fb, L.dframe, &rc, [&](T* part, int nf, int) {
+                return blur_ch_batch_impl(ctx, part, part, nf, rows, cols, channels, sigma, opts, lay);
+            }))
+            return rc;
+        if (int rc = ch_copy_source(ctx, &d_src, d_dst, nframes, nframes, rows, rowbytes, L)) return rc;
     }
     if (p.fx) {
         ctx->last_family = 6;
-        if constexpr (ffk) return run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels), L);
-        else return channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, nframes, rows, cols, p, nullptr, fw_chsel_all(3), &L)
-                                  : run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels), L);
+        return run_ch_fused<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p, fw_chsel_all(channels), L);
     }
-    blur_opts o;
-    blur_opts_default(&o);
-    if (opts) o = *opts;
-    o.engine = BLUR_ENGINE_FFT;
+    const blur_opts o = with_engine(opts, BLUR_ENGINE_FFT);
     if (int rc = run_planes(ctx, d_src, d_dst, nframes, rows, cols, channels, sigma, &o, L)) return rc;
     ctx->last_family = 0;
     ctx->engine_note = note;
     return BLUR_OK;
 }
 
-// blur_gaussian_{u8,f32,u16,f16,bf16}_host: one frame through the context's host staging buffer (source and destination apart: no in-place copy)
-template <typename T>
-static int blur_ch_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+// One frame through the context's host staging buffer: in, body(d_src, d_dst) on its two halves (source and destination apart: the
+// fused engine reads its neighbours' pixels while it writes and would otherwise copy an in-place frame into its workspace), out
+template <typename Body>
+static int blur_through_host_stage(blur_ctx* ctx, const void* src, void* dst, size_t bytes, Body body)
 {
-    if (int rc = check_ch_args(ctx, src, dst, 1, rows, cols, channels, sigma)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = static_cast<size_t>(rows) * cols * channels * sizeof(T), half = (bytes + 255) & ~static_cast<size_t>(255);
+    const size_t half = (bytes + 255) & ~static_cast<size_t>(255);
     void* dv = nullptr;
     if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;
     char* d = static_cast<char*>(dv);
     int rc = BLUR_OK;
     hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) rc = blur_ch_batch_impl(ctx, reinterpret_cast<const T*>(d), reinterpret_cast<T*>(d + half), 1, rows, cols, channels, sigma, opts);
+    if (e == hipSuccess) rc = body(d, d + half);
     if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
     return rc;
+}
+
+// blur_gaussian_{u8,f32,u16,f16,bf16}_host
+template <typename T>
+static int blur_ch_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols, int channels, double sigma, const blur_opts* opts)
+{
+    if (int rc = check_ch_args(ctx, src, dst, 1, rows, cols, channels, sigma)) return rc;
+    return blur_through_host_stage(ctx, src, dst, static_cast<size_t>(rows) * cols * channels * sizeof(T), [&](char* s, char* d) {
+        return blur_ch_batch_impl(ctx, reinterpret_cast<const T*>(s), reinterpret_cast<T*>(d), 1, rows, cols, channels, sigma, opts);
+    });
 }
 
 // ======================================================================================
@@ -2396,23 +2450,23 @@ static int launch_chan_copy(blur_ctx* ctx, const T* src, T* dst, size_t nelem, i
 // the sigma = 0 channels (out of place only), and per group the whole pre-pass (the quirk's sums are weighted by the pad's parity and
 // the strips are as wide as the pad: both belong to the group) and the fused launch over the group's channels, or the plane path
 // over them.  The strips and sums workspaces are reused from group to group.
-// two_ok (blur_nv_batch_impl: the interleaved Cb/Cr plane of an NV12 / P016 surface): channels = 2 is legal, u8 and u16 only.
+// part.two_ok (blur_nv_batch_impl: the interleaved Cb/Cr plane of an NV12 / P016 surface): channels = 2 is legal, u8 and u16 only.
+struct ChSigmasPart { bool two_ok = false; };
+
 template <typename T>
 static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts,
-                                     const ChLayout* lay = nullptr, bool two_ok = false)
+                                     const ChLayout* lay = nullptr, const ChSigmasPart& part = {})
 {
-    constexpr bool u8 = std::is_same_v<T, uint8_t>;
     SigmaGroups sg;
     if (lay)
-        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay, false, two_ok)) return rc;
-    if (int rc = check_ch_sigmas_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, sg, two_ok)) return rc;
+        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay, false, part.two_ok)) return rc;
+    if (int rc = check_ch_sigmas_args(ctx, d_src, d_dst, nframes, rows, cols, channels, sigmas, sg, part.two_ok)) return rc;
     // (two channels have no scalar entry: one group over both is a launch of this driver)
     if (sg.ngroups == 1 && !sg.zero_mask && channels != 2) return blur_ch_batch_impl(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[0], opts, lay);
     ChLayout L = lay ? *lay : ch_packed(rows, cols, channels, sizeof(T));
     if (nframes == 1) L.sframe = L.dframe = 0;
-    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
-    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, (std::string(ch_type_name<T>()) + " images, one sigma per channel: engine must be AUTO, FUSED or FFT").c_str());
+    const int choice = ch_engine_choice(ctx, opts, ch_type_name<T>(), " images, one sigma per channel");
+    if (choice < 0) return BLUR_ERR_UNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Prepared p[4];
     std::string why[4];
@@ -2420,43 +2474,27 @@ static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, in
         if (int rc = choose_ch_engine<T>(ctx, rows, cols, channels, sg.sigma[g], opts, choice, p[g], why[g], L)) return rc;
     ctx->engine_note.clear();
     if (nframes == 0) return BLUR_OK;
-    const bool in_place = d_src == d_dst && L.spitch == L.dpitch && L.sframe == L.dframe;
+    const bool in_place = ch_in_place(d_src, d_dst, L);
     if (in_place && sg.ngroups == 0) return BLUR_OK;            // every channel is left as it is
     const size_t rowbytes = static_cast<size_t>(cols) * channels * sizeof(T), fe = static_cast<size_t>(rows) * cols * channels, fb = fe * sizeof(T);
     const bool packed = L.spitch == rowbytes && L.dpitch == rowbytes && (nframes == 1 || (L.sframe == fb && L.dframe == fb));
-    if (ch_spans_overlap(d_src, d_dst, nframes, rows, rowbytes, L)) {
-        if (in_place) {             // in parts of at most 1 GiB (a part's result never touches a later part's source)
-            const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
-            if (static_cast<size_t>(nframes) > cap) {
-                for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
-                    const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
-                    T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * L.dframe);
-                    if (int rc = blur_ch_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas, opts, lay, two_ok)) return rc;
-                }
-                return BLUR_OK;
-            }
-        }
-        if (int rc = ch_copy_source(ctx, &d_src, nframes, rows, rowbytes, L)) return rc;
-    }
+    int parts_rc;
+    if (in_place && ch_in_place_parts(d_dst, nframes, fb, L.dframe, &parts_rc, [&](T* at, int nf, int) {
+            return blur_ch_sigmas_batch_impl(ctx, at, at, nf, rows, cols, channels, sigmas, opts, lay, part);
+        }))
+        return parts_rc;
+    if (int rc = ch_copy_source(ctx, &d_src, d_dst, nframes, nframes, rows, rowbytes, L)) return rc;
     if (!in_place) {
         if (!packed) {                  // a pitched destination: the samples of the sigma = 0 channels only, row by row
             if (int rc = launch_chan_copy_rows<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.zero_mask, L)) return rc;
         } else if (sg.ngroups == 0) HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_src, fb * nframes, hipMemcpyDeviceToDevice, ctx->stream));
         else if (int rc = launch_chan_copy<T>(ctx, d_src, d_dst, fe * nframes, channels, sg.zero_mask)) return rc;       // (every other channel is written below)
     }
-    blur_opts fft_opts;
-    blur_opts_default(&fft_opts);
-    if (opts) fft_opts = *opts;
-    fft_opts.engine = BLUR_ENGINE_FFT;
+    const blur_opts fft_opts = with_engine(opts, BLUR_ENGINE_FFT);
     std::string note;
     for (int g = 0; g < sg.ngroups; ++g) {
         if (p[g].fx) {
-            const FwChSel chsel = fw_chsel_mask(sg.mask[g], channels);
-            int rc;
-            if constexpr (!u8) rc = run_ff<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], chsel, L);
-            else rc = channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, nframes, rows, cols, p[g], nullptr, chsel, &L)
-                                    : run_fc_u8(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], chsel, L);
-            if (rc) return rc;
+            if (int rc = run_ch_fused<T>(ctx, d_src, d_dst, nframes, rows, cols, channels, p[g], fw_chsel_mask(sg.mask[g], channels), L)) return rc;
         } else {
             if (int rc = run_planes(ctx, d_src, d_dst, nframes, rows, cols, channels, sg.sigma[g], &fft_opts, L, sg.mask[g])) return rc;
             char head[96];
@@ -2470,24 +2508,15 @@ static int blur_ch_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, in
     return BLUR_OK;
 }
 
-// blur_gaussian_*_sigmas_host: one frame through the context's host staging buffer (as blur_ch_host)
+// blur_gaussian_*_sigmas_host (as blur_ch_host)
 template <typename T>
 static int blur_ch_sigmas_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts)
 {
     SigmaGroups sg;
     if (int rc = check_ch_sigmas_args(ctx, src, dst, 1, rows, cols, channels, sigmas, sg)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = static_cast<size_t>(rows) * cols * channels * sizeof(T), half = (bytes + 255) & ~static_cast<size_t>(255);
-    void* dv = nullptr;
-    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;
-    char* d = static_cast<char*>(dv);
-    int rc = BLUR_OK;
-    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) rc = blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const T*>(d), reinterpret_cast<T*>(d + half), 1, rows, cols, channels, sigmas, opts);
-    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
-    return rc;
+    return blur_through_host_stage(ctx, src, dst, static_cast<size_t>(rows) * cols * channels * sizeof(T), [&](char* s, char* d) {
+        return blur_ch_sigmas_batch_impl(ctx, reinterpret_cast<const T*>(s), reinterpret_cast<T*>(d), 1, rows, cols, channels, sigmas, opts);
+    });
 }
 
 // ======================================================================================
@@ -2526,20 +2555,53 @@ static int nv_layout_status(const NvSurface& s, size_t es, int nframes, int rows
     return BLUR_OK;
 }
 
-static int nv_status(const NvSurface& s, size_t es, int nframes, int rows, int cols, const double* sigmas, const char** why)
+// The n sigmas of a call, every `period` of them one luma sigma and then the chroma sigmas (in chroma pixels): each finite and >= 0,
+// and the pad of each positive one within its plane
+static int nv_sigmas_status(const double* sigmas, int n, int period, int rows, int cols, const char* luma_pad, const char* chroma_pad, const char** why)
 {
     auto no = [&](int rc, const char* text) { *why = text; return rc; };
-    if (int rc = nv_layout_status(s, es, nframes, rows, cols, sigmas, why)) return rc;
-    for (int p = 0; p < 3; ++p)
-        if (!(sigmas[p] >= 0) || !std::isfinite(sigmas[p])) return no(BLUR_ERR_INVALID, "every sigma must be finite and positive, or 0 for a plane that is left as it is");
-    for (int p = 0; p < 3; ++p) {
-        if (sigmas[p] == 0) continue;
-        const int r = p ? rows / 2 : rows, c = p ? cols / 2 : cols;
-        const Sizing sz = pffft_sizing(r, c, sigmas[p]);
-        if (sz.pad > r - 1 || sz.pad > c - 1)
-            return no(BLUR_ERR_UNSUPPORTED, p ? "chroma pad > min(rows / 2, cols / 2) - 1: reflect-101 would read outside the plane (sigmas[1], sigmas[2] are in chroma pixels)"
-                                              : "luma pad > min(rows, cols) - 1: reflect-101 would read outside the plane");
+    for (int i = 0; i < n; ++i)
+        if (!(sigmas[i] >= 0) || !std::isfinite(sigmas[i])) return no(BLUR_ERR_INVALID, "every sigma must be finite and positive, or 0 for a plane that is left as it is");
+    for (int i = 0; i < n; ++i) {
+        if (sigmas[i] == 0) continue;
+        const bool chroma = i % period != 0;
+        const int r = chroma ? rows / 2 : rows, c = chroma ? cols / 2 : cols;
+        const Sizing sz = pffft_sizing(r, c, sigmas[i]);
+        if (sz.pad > r - 1 || sz.pad > c - 1) return no(BLUR_ERR_UNSUPPORTED, chroma ? chroma_pad : luma_pad);
     }
+    return BLUR_OK;
+}
+
+static int nv_status(const NvSurface& s, size_t es, int nframes, int rows, int cols, const double* sigmas, const char** why)
+{
+    if (int rc = nv_layout_status(s, es, nframes, rows, cols, sigmas, why)) return rc;
+    return nv_sigmas_status(sigmas, 3, 3, rows, cols, "luma pad > min(rows, cols) - 1: reflect-101 would read outside the plane",
+                            "chroma pad > min(rows / 2, cols / 2) - 1: reflect-101 would read outside the plane (sigmas[1], sigmas[2] are in chroma pixels)", why);
+}
+
+// the two planes of a batch of surfaces as the per-channel drivers take them: the layouts, and the chroma plane's size in pairs
+struct NvPlanes { ChLayout Ly, Luv; int crows, ccols; };
+static NvPlanes nv_planes(NvSurface s, int nframes, int rows, int cols)
+{
+    if (nframes <= 1) s.sy_frame = s.suv_frame = s.dy_frame = s.duv_frame = 0;           // (a single frame's strides address nothing)
+    return NvPlanes{ { s.spitch, s.sy_frame, s.dpitch, s.dy_frame }, { s.spitch, s.suv_frame, s.dpitch, s.duv_frame }, rows / 2, cols / 2 };
+}
+
+// The luma part and the chroma part of a call, each a call of a per-channel driver, and what blur_last_engine says of both (blur_y,
+// blur_c: the part has a sigma > 0, so it sets the family, and its note is empty where that is 6).  family 6: every blurred plane (of
+// every frame) ran on the fused kernel; 0: some took the plane path, and the note names them
+template <typename Luma, typename Chroma>
+static int nv_run_parts(blur_ctx* ctx, bool blur_y, bool blur_c, const char* luma_prefix, Luma luma, Chroma chroma)
+{
+    std::string note;
+    ctx->engine_note.clear();
+    if (int rc = luma()) return rc;
+    if (blur_y && ctx->last_family != 6) note = luma_prefix + ctx->engine_note;
+    ctx->engine_note.clear();
+    if (int rc = chroma()) return rc;
+    if (blur_c && ctx->last_family != 6) note += (note.empty() ? "" : "; ") + std::string("chroma: ") + ctx->engine_note;
+    ctx->last_family = note.empty() ? 6 : 0;
+    ctx->engine_note = note;
     return BLUR_OK;
 }
 
@@ -2549,33 +2611,24 @@ static int blur_nv_batch_impl(blur_ctx* ctx, NvSurface s, int nframes, int rows,
     const char* why = nullptr;
     if (int rc = nv_status(s, sizeof(T), nframes, rows, cols, sigmas, &why)) return fail(ctx, rc, why);
     if (!ctx) return BLUR_ERR_INVALID;
-    if (nframes <= 1) s.sy_frame = s.suv_frame = s.dy_frame = s.duv_frame = 0;           // (a single frame's strides address nothing)
-    const ChLayout Ly{ s.spitch, s.sy_frame, s.dpitch, s.dy_frame }, Luv{ s.spitch, s.suv_frame, s.dpitch, s.duv_frame };
-    const int crows = rows / 2, ccols = cols / 2;
-    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
-    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, "NV12 / P016 surfaces: engine must be AUTO, FUSED or FFT");
+    const NvPlanes pl = nv_planes(s, nframes, rows, cols);
+    const int choice = ch_engine_choice(ctx, opts, "NV12 / P016", " surfaces");
+    if (choice < 0) return BLUR_ERR_UNSUPPORTED;
     if (choice == BLUR_ENGINE_FUSED) {          // every plane's engine before the first launch: a refused call has written nothing
         for (int p = 0; p < 3; ++p) {
             if (sigmas[p] == 0 || (p == 2 && sigmas[2] == sigmas[1])) continue;
             Prepared pr;
             std::string note;
-            if (int rc = choose_ch_engine<T>(ctx, p ? crows : rows, p ? ccols : cols, p ? 2 : 1, sigmas[p], opts, choice, pr, note, p ? Luv : Ly)) return rc;
+            if (int rc = choose_ch_engine<T>(ctx, p ? pl.crows : rows, p ? pl.ccols : cols, p ? 2 : 1, sigmas[p], opts, choice, pr, note, p ? pl.Luv : pl.Ly)) return rc;
         }
     }
     if (nframes == 0) return BLUR_OK;
-    std::string note;
-    const bool blur_y = sigmas[0] > 0, blur_c = sigmas[1] > 0 || sigmas[2] > 0;
-    ctx->engine_note.clear();
-    if (int rc = blur_ch_sigmas_batch_impl<T>(ctx, static_cast<const T*>(s.sy), static_cast<T*>(s.dy), nframes, rows, cols, 1, sigmas, opts, &Ly)) return rc;
-    if (blur_y && ctx->last_family != 6) note = "luma on the plane path: " + ctx->engine_note;
-    ctx->engine_note.clear();
-    if (int rc = blur_ch_sigmas_batch_impl<T>(ctx, static_cast<const T*>(s.suv), static_cast<T*>(s.duv), nframes, crows, ccols, 2, sigmas + 1, opts, &Luv, true)) return rc;
-    if (blur_c && ctx->last_family != 6) note += (note.empty() ? "" : "; ") + std::string("chroma: ") + ctx->engine_note;
-    // family 6: every blurred plane ran on the fused kernel; 0: one took the plane path, and the note names it
-    ctx->last_family = note.empty() ? 6 : 0;
-    ctx->engine_note = note;
-    return BLUR_OK;
+    ChSigmasPart chroma;
+    chroma.two_ok = true;
+    return nv_run_parts(
+        ctx, sigmas[0] > 0, sigmas[1] > 0 || sigmas[2] > 0, "luma on the plane path: ",
+        [&] { return blur_ch_sigmas_batch_impl<T>(ctx, static_cast<const T*>(s.sy), static_cast<T*>(s.dy), nframes, rows, cols, 1, sigmas, opts, &pl.Ly); },
+        [&] { return blur_ch_sigmas_batch_impl<T>(ctx, static_cast<const T*>(s.suv), static_cast<T*>(s.duv), nframes, pl.crows, pl.ccols, 2, sigmas + 1, opts, &pl.Luv, chroma); });
 }
 
 // blur_gaussian_{nv12,p016}_host: one packed surface (rows x cols luma samples, then rows / 2 rows of cols chroma samples) through the
@@ -2589,18 +2642,9 @@ static int blur_nv_host(blur_ctx* ctx, const T* src, T* dst, int rows, int cols,
     const char* why = nullptr;
     if (int rc = nv_status(s, sizeof(T), 1, rows, cols, sigmas, &why)) return fail(ctx, rc, why);
     if (!ctx) return BLUR_ERR_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = ybytes + ybytes / 2, half = (bytes + 255) & ~static_cast<size_t>(255);
-    void* dv = nullptr;
-    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;
-    char* d = static_cast<char*>(dv);
-    int rc = BLUR_OK;
-    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) rc = blur_nv_batch_impl<T>(ctx, NvSurface{ d, d + ybytes, d + half, d + half + ybytes, pitch, 0, 0, pitch, 0, 0 }, 1, rows, cols, sigmas, opts);
-    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
-    return rc;
+    return blur_through_host_stage(ctx, src, dst, ybytes + ybytes / 2, [&](char* sd, char* dd) {
+        return blur_nv_batch_impl<T>(ctx, NvSurface{ sd, sd + ybytes, dd, dd + ybytes, pitch, 0, 0, pitch, 0, 0 }, 1, rows, cols, sigmas, opts);
+    });
 }
 
 // ======================================================================================
@@ -2689,47 +2733,40 @@ static int fs_upload(blur_ctx* ctx, const std::vector<unsigned char>& host)
 }
 
 // One driver over the five element types, next to blur_ch_sigmas_batch_impl (u16 and the half types take run_ff<T> as they do there).
-// Every distinct sigma gets the engine blur_ch_batch_impl's rules give it (the rules of choose_ch_engine;
+// Every distinct sigma gets the engine blur_ch_batch_impl's rules give it (prepare's for the pad and the frame, then ch_fused_refusal;
 // u8 with three channels: those of one and four channels, on fw_blur_u8<NKB, Q, 3> -- never the u8c3 entry, whatever the sigmas: a
 // frame's bytes depend on its pixels, its sigma and opts alone) and its fragments, taps and gains from mx_host_tables, the code
 // behind the scalar entries' cached tables; nothing goes into ctx->mx_tables.  All of that happens before the first launch.  Then, on
 // the one stream: the copy of overlapping sources, the copies of the sigma = 0 frames (out of place only), the upload of the call's
 // table, and per window class the pre-pass and ONE fused launch over the class's frames (their list: FwFrame); the frames without
 // a fused kernel run one by one on the plane path.  The strips and sums workspaces are reused from class to class.
-// note: null for the call itself; the parts of a large in-place batch add to their caller's
+// note: null for the call itself; the parts of a large in-place batch add to their caller's, frame0 being their first frame in its batch
 // two_ok (blur_nv_frame_sigmas_batch_impl: the interleaved Cb/Cr plane of an NV12 / P016 surface): channels = 2 is legal, u8 and u16 only.
 // plan_only: return once every sigma has its engine, before anything is written (that caller's check of one part ahead of the other's
 // launches)
+struct ChFramePart { FramePlaneNote* note = nullptr; int frame0 = 0; bool two_ok = false, plan_only = false; };
+
 template <typename T>
 static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_dst, int nframes, int rows, int cols, int channels, const double* sigmas, const blur_opts* opts,
-                                           const ChLayout* lay = nullptr, FramePlaneNote* note = nullptr, int frame0 = 0, bool two_ok = false, bool plan_only = false)
+                                           const ChLayout* lay = nullptr, const ChFramePart& part = {})
 {
-    constexpr bool u8 = std::is_same_v<T, uint8_t>, u16 = std::is_same_v<T, uint16_t>, half = ff_is_half_v<T>, ffk = !u8;
     FrameSigmaPlan pl;
     if (lay)
-        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay, true, two_ok)) return rc;
-    {
-        const char* why = nullptr;
-        if (int rc = frame_sigmas_status(d_src, d_dst, nframes, rows, cols, channels, sigmas, pl, &why, two_ok)) return fail(ctx, rc, why);
-        if (!ctx) return BLUR_ERR_INVALID;
-    }
+        if (int rc = check_ch_layout(ctx, nframes, rows, cols, channels, sizeof(T), *lay, true, part.two_ok)) return rc;
+    const char* bad = nullptr;
+    if (int rc = frame_sigmas_status(d_src, d_dst, nframes, rows, cols, channels, sigmas, pl, &bad, part.two_ok)) return fail(ctx, rc, bad);
+    if (!ctx) return BLUR_ERR_INVALID;
     ChLayout L = lay ? *lay : ch_packed(rows, cols, channels, sizeof(T));
     if (nframes == 1) L.sframe = L.dframe = 0;
-    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
-    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, (std::string(ch_type_name<T>()) + " images, one sigma per frame: engine must be AUTO, FUSED or FFT").c_str());
+    const int choice = ch_engine_choice(ctx, opts, ch_type_name<T>(), " images, one sigma per frame");
+    if (choice < 0) return BLUR_ERR_UNSUPPORTED;
     const bool quirk = opts ? opts->nyquist_quirk != 0 : true;
     const size_t rowbytes = static_cast<size_t>(cols) * channels * sizeof(T), fb = rowbytes * rows;
     // the engine and the tables of every distinct sigma
     const int nslots = static_cast<int>(pl.slots.size());
     std::vector<MxHostTables> tabs(nslots);
-    std::vector<const char*> why(nslots, nullptr);
     std::vector<char> fused(nslots, 0);
-    const std::string kind = std::string("fused kernel for ") + ch_type_name<T>() + " images: ";
-    const std::string no_class = kind + "pad 153 .. 168 has a kernel for 1 channel only";
-    const std::string no_contract = kind + (half ? "pad 105 .. 168 is outside the library's own choice, as for float32; ask for it with engine = FUSED"
-                                            : u16 ? "pad 105 .. 168 exceeds 1e-6 of full scale on full-scale content (1.2e-6); ask for it with engine = FUSED"
-                                                  : "pad 105 .. 168 exceeds 1e-6 max|x| on full-scale content (1.2e-6); ask for it with engine = FUSED");
+    std::string plane_why;          // of the first sigma that stays on the plane path: the slots' order makes its first frame the first of those
     for (int s = 0; s < nslots && choice != BLUR_ENGINE_FFT; ++s) {
         const FrameSigmaPlan::Slot& sl = pl.slots[s];
         const char* w = sl.nkb ? fx_frame_limits(rows, cols, quirk) : "fused matrix-core engine: no kernel instantiated for this pad";
@@ -2737,41 +2774,33 @@ static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_d
             std::vector<float> karr[2];
             if (mx_kernel_arrays(sl.sigma, sl.sz, nullptr, karr, &w) == BLUR_OK) (void)mx_host_tables(karr, sl.sz, sl.nkb, tabs[s], &w, false);
         }
-        // (the texts of choose_ch_engine, by type)
-        if (!w && ffk && !ff_class_ok_t<T>(sl.nkb, channels)) w = no_class.c_str();
-        else if (!w && ffk && choice == BLUR_ENGINE_AUTO && !ff_class_in_contract(sl.nkb)) w = no_contract.c_str();
-        else if (!w && std::max(ch_frame_span(rows, L.spitch, rowbytes), ch_frame_span(rows, L.dpitch, rowbytes)) > 0xfffff000ull)
-            w = "fused matrix-core engine: frame too large for 32-bit offsets";
-        if (w && choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, w);
-        why[s] = w;
-        fused[s] = w ? 0 : 1;
+        const std::string why = w ? std::string(w) : ch_fused_refusal<T>(sl.nkb, rows, cols, channels, choice, L, true);
+        if (!why.empty() && choice == BLUR_ENGINE_FUSED) return fail(ctx, BLUR_ERR_UNSUPPORTED, why.c_str());
+        fused[s] = why.empty();
+        if (!fused[s] && plane_why.empty()) plane_why = why;
     }
-    if (plan_only) return BLUR_OK;
-    if (!note) ctx->engine_note.clear();
+    if (part.plan_only) return BLUR_OK;
+    if (!part.note) ctx->engine_note.clear();
     if (nframes == 0) return BLUR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool in_place = d_src == d_dst && L.spitch == L.dpitch && L.sframe == L.dframe;
+    const bool in_place = ch_in_place(d_src, d_dst, L);
     if (in_place && nslots == 0) return BLUR_OK;                  // every frame is left as it is
     FramePlaneNote mine;
-    FramePlaneNote& pn = note ? *note : mine;
-    if (ch_spans_overlap(d_src, d_dst, nframes, rows, rowbytes, L)) {
-        if (in_place) {             // in parts of at most 1 GiB (a part's result never touches a later part's source)
-            const size_t cap = std::max<size_t>(1, (static_cast<size_t>(1) << 30) / fb);
-            if (static_cast<size_t>(nframes) > cap) {
-                for (int f0 = 0; f0 < nframes; f0 += static_cast<int>(cap)) {
-                    const int nf = std::min<int>(static_cast<int>(cap), nframes - f0);
-                    T* part = reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f0) * L.dframe);
-                    if (int rc = blur_ch_frame_sigmas_batch_impl(ctx, part, part, nf, rows, cols, channels, sigmas + f0, opts, lay, &pn, frame0 + f0, two_ok)) return rc;
-                }
-                nframes = 0;                                       // (the note is written below)
-            }
-        }
-        // one gathered copy of the source; a broadcast source (frame stride 0) is one frame
-        const bool broadcast = nframes > 1 && L.sframe == 0;
-        if (nframes > 0) {
-            if (int rc = ch_copy_source(ctx, &d_src, broadcast ? 1 : nframes, rows, rowbytes, L)) return rc;
-            if (broadcast || nframes == 1) L.sframe = 0;
-        }
+    FramePlaneNote& pn = part.note ? *part.note : mine;
+    int parts_rc;
+    if (in_place && ch_in_place_parts(d_dst, nframes, fb, L.dframe, &parts_rc, [&](T* at, int nf, int f0) {
+            ChFramePart sub = part;
+            sub.note = &pn, sub.frame0 += f0;
+            return blur_ch_frame_sigmas_batch_impl(ctx, at, at, nf, rows, cols, channels, sigmas + f0, opts, lay, sub);
+        })) {
+        if (parts_rc) return parts_rc;
+        nframes = 0;                                               // (the note is written below)
+    }
+    // one gathered copy of an overlapping source; a broadcast source (frame stride 0) is one frame
+    const bool broadcast = nframes > 1 && L.sframe == 0;
+    if (nframes > 0) {
+        if (int rc = ch_copy_source(ctx, &d_src, d_dst, nframes, broadcast ? 1 : nframes, rows, rowbytes, L)) return rc;
+        if (broadcast || nframes == 1) L.sframe = 0;
     }
     auto src_of = [&](int f) { return reinterpret_cast<const T*>(reinterpret_cast<const char*>(d_src) + static_cast<size_t>(f) * L.sframe); };
     auto dst_of = [&](int f) { return reinterpret_cast<T*>(reinterpret_cast<char*>(d_dst) + static_cast<size_t>(f) * L.dframe); };
@@ -2834,27 +2863,20 @@ static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_d
             p.mx_quirk = quirk;
             const FwFrame* ft = static_cast<const FwFrame*>(ctx->fs_table) + at;
             at += n;
-            int rc;
-            if constexpr (ffk) rc = run_ff<T>(ctx, d_src, d_dst, n, rows, cols, channels, p, fw_chsel_all(channels), L, ft);
-            else rc = channels == 3 ? run_fx_u8c3(ctx, d_src, d_dst, n, rows, cols, p, nullptr, fw_chsel_all(3), &L, ft)
-                                    : run_fc_u8(ctx, d_src, d_dst, n, rows, cols, channels, p, fw_chsel_all(channels), L, ft);
-            if (rc) return rc;
+            if (int rc = run_ch_fused<T>(ctx, d_src, d_dst, n, rows, cols, channels, p, fw_chsel_all(channels), L, ft)) return rc;
         }
     }
     // the frames without a fused kernel, one by one on the plane path
-    blur_opts fft_opts;
-    blur_opts_default(&fft_opts);
-    if (opts) fft_opts = *opts;
-    fft_opts.engine = BLUR_ENGINE_FFT;
+    const blur_opts fft_opts = with_engine(opts, BLUR_ENGINE_FFT);
     ChLayout L1 = L;
     L1.sframe = L1.dframe = 0;
     for (int f = 0; f < nframes; ++f) {
         const int s = pl.slot_of[f];
         if (s < 0 || fused[s]) continue;
         if (int rc = run_planes(ctx, src_of(f), dst_of(f), 1, rows, cols, channels, pl.slots[s].sigma, &fft_opts, L1)) return rc;
-        if (pn.count++ == 0) { pn.first = frame0 + f; pn.sigma = pl.slots[s].sigma; pn.why = why[s] ? why[s] : ""; }
+        if (pn.count++ == 0) { pn.first = part.frame0 + f; pn.sigma = pl.slots[s].sigma; pn.why = plane_why; }
     }
-    if (!note) {
+    if (!part.note) {
         // family 6: every blurred frame ran on the fused kernel; 0: frames took the plane path, and the note names the first
         ctx->last_family = pn.count ? 0 : 6;
         ctx->engine_note.clear();
@@ -2875,19 +2897,9 @@ static int blur_ch_frame_sigmas_batch_impl(blur_ctx* ctx, const T* d_src, T* d_d
 // ======================================================================================
 static int nv_frame_sigmas_status(const NvSurface& s, size_t es, int nframes, int rows, int cols, const double* sigmas, const char** why)
 {
-    auto no = [&](int rc, const char* text) { *why = text; return rc; };
     if (int rc = nv_layout_status(s, es, nframes, rows, cols, sigmas, why)) return rc;
-    for (int i = 0; i < 2 * nframes; ++i)
-        if (!(sigmas[i] >= 0) || !std::isfinite(sigmas[i])) return no(BLUR_ERR_INVALID, "every sigma must be finite and positive, or 0 for a plane that is left as it is");
-    for (int i = 0; i < 2 * nframes; ++i) {
-        if (sigmas[i] == 0) continue;
-        const int r = (i & 1) ? rows / 2 : rows, c = (i & 1) ? cols / 2 : cols;
-        const Sizing sz = pffft_sizing(r, c, sigmas[i]);
-        if (sz.pad > r - 1 || sz.pad > c - 1)
-            return no(BLUR_ERR_UNSUPPORTED, (i & 1) ? "chroma pad > min(rows / 2, cols / 2) - 1 for one of the frames: reflect-101 would read outside the plane (chroma sigmas are in chroma pixels)"
-                                                    : "luma pad > min(rows, cols) - 1 for one of the frames: reflect-101 would read outside the plane");
-    }
-    return BLUR_OK;
+    return nv_sigmas_status(sigmas, 2 * nframes, 2, rows, cols, "luma pad > min(rows, cols) - 1 for one of the frames: reflect-101 would read outside the plane",
+                            "chroma pad > min(rows / 2, cols / 2) - 1 for one of the frames: reflect-101 would read outside the plane (chroma sigmas are in chroma pixels)", why);
 }
 
 template <typename T>
@@ -2896,12 +2908,9 @@ static int blur_nv_frame_sigmas_batch_impl(blur_ctx* ctx, NvSurface s, int nfram
     const char* why = nullptr;
     if (int rc = nv_frame_sigmas_status(s, sizeof(T), nframes, rows, cols, sigmas, &why)) return fail(ctx, rc, why);
     if (!ctx) return BLUR_ERR_INVALID;
-    if (nframes <= 1) s.sy_frame = s.suv_frame = s.dy_frame = s.duv_frame = 0;           // (a single frame's strides address nothing)
-    const ChLayout Ly{ s.spitch, s.sy_frame, s.dpitch, s.dy_frame }, Luv{ s.spitch, s.suv_frame, s.dpitch, s.duv_frame };
-    const int crows = rows / 2, ccols = cols / 2;
-    const int choice = opts ? opts->engine : BLUR_ENGINE_AUTO;
-    if (choice != BLUR_ENGINE_AUTO && choice != BLUR_ENGINE_FUSED && choice != BLUR_ENGINE_FFT)
-        return fail(ctx, BLUR_ERR_UNSUPPORTED, "NV12 / P016 surfaces: engine must be AUTO, FUSED or FFT");
+    const NvPlanes pl = nv_planes(s, nframes, rows, cols);
+    const int choice = ch_engine_choice(ctx, opts, "NV12 / P016", " surfaces");
+    if (choice < 0) return BLUR_ERR_UNSUPPORTED;
     std::vector<double> sy(nframes), sc(nframes);
     bool blur_y = false, blur_c = false;
     for (int f = 0; f < nframes; ++f) {
@@ -2916,20 +2925,15 @@ static int blur_nv_frame_sigmas_batch_impl(blur_ctx* ctx, NvSurface s, int nfram
     T* dst_uv = static_cast<T*>(s.duv);
     // every chroma frame's engine before the luma part's first launch (the luma part chooses its own before it launches): a refused
     // call has written nothing.  Only FUSED refuses.
+    ChFramePart chroma, chroma_plan;
+    chroma.two_ok = chroma_plan.two_ok = true;
+    chroma_plan.plan_only = true;
     if (choice == BLUR_ENGINE_FUSED)
-        if (int rc = blur_ch_frame_sigmas_batch_impl<T>(ctx, src_uv, dst_uv, nframes, crows, ccols, 2, sc.data(), opts, &Luv, nullptr, 0, true, true)) return rc;
+        if (int rc = blur_ch_frame_sigmas_batch_impl<T>(ctx, src_uv, dst_uv, nframes, pl.crows, pl.ccols, 2, sc.data(), opts, &pl.Luv, chroma_plan)) return rc;
     if (nframes == 0) return BLUR_OK;
-    std::string note;
-    ctx->engine_note.clear();
-    if (int rc = blur_ch_frame_sigmas_batch_impl<T>(ctx, src_y, dst_y, nframes, rows, cols, 1, sy.data(), opts, &Ly)) return rc;
-    if (blur_y && !ctx->engine_note.empty()) note = "luma: " + ctx->engine_note;
-    ctx->engine_note.clear();
-    if (int rc = blur_ch_frame_sigmas_batch_impl<T>(ctx, src_uv, dst_uv, nframes, crows, ccols, 2, sc.data(), opts, &Luv, nullptr, 0, true)) return rc;
-    if (blur_c && !ctx->engine_note.empty()) note += (note.empty() ? "" : "; ") + std::string("chroma: ") + ctx->engine_note;
-    // family 6: every blurred plane of every frame ran on the fused kernel; 0: some took the plane path, and the note names them
-    ctx->last_family = note.empty() ? 6 : 0;
-    ctx->engine_note = note;
-    return BLUR_OK;
+    return nv_run_parts(
+        ctx, blur_y, blur_c, "luma: ", [&] { return blur_ch_frame_sigmas_batch_impl<T>(ctx, src_y, dst_y, nframes, rows, cols, 1, sy.data(), opts, &pl.Ly); },
+        [&] { return blur_ch_frame_sigmas_batch_impl<T>(ctx, src_uv, dst_uv, nframes, pl.crows, pl.ccols, 2, sc.data(), opts, &pl.Luv, chroma); });
 }
 
 // ======================================================================================
@@ -3631,20 +3635,9 @@ int blur_gaussian_u8c3_host(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int
 {
     if (!ctx) return BLUR_ERR_INVALID;
     if (!src || !dst || rows <= 0 || cols <= 0) return fail(ctx, BLUR_ERR_INVALID, "null image or non-positive size");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = static_cast<size_t>(rows) * cols * 3, half = (bytes + 255) & ~static_cast<size_t>(255);
-    void* dv = nullptr;
-    // two device images, source and destination: the fused engine reads its neighbours' pixels while it writes and would otherwise
-    // copy an in-place frame into its workspace first
-    if (int rc0 = ensure_host_stage(ctx, 2 * half, &dv)) return rc0;
-    uint8_t* d = static_cast<uint8_t*>(dv);
-    int rc = BLUR_OK;
-    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) rc = blur_gaussian_u8c3_dev(ctx, d, d + half, rows, cols, sigma, opts);
-    if (e == hipSuccess && rc == BLUR_OK) e = hipMemcpyAsync(dst, d + half, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->err = std::string("host blur: ") + hipGetErrorString(e); return BLUR_ERR_HIP; }
-    return rc;
+    return blur_through_host_stage(ctx, src, dst, static_cast<size_t>(rows) * cols * 3, [&](char* s, char* d) {
+        return blur_gaussian_u8c3_dev(ctx, reinterpret_cast<const uint8_t*>(s), reinterpret_cast<uint8_t*>(d), rows, cols, sigma, opts);
+    });
 }
 
 int blur_gaussian_u8c3_host_batch(blur_ctx* ctx, const uint8_t* src, uint8_t* dst, int nframes, int rows, int cols, double sigma,
@@ -4272,20 +4265,27 @@ int blur_fastboxblur_u8_batch_multi_host(blur_multi* m, uint8_t* inout, int nfra
 
 // blur_gaussian_{u8,f32,u16,f16,bf16}_batch_multi_*: the frames of a batch sharded over the devices (a template: C++ linkage)
 extern "C++" {
+// the shards of a per-channel batch whose arguments have been checked: body(ctx, in, out, n) queues one shard's n frames
+template <typename T, typename Body>
+static int blur_ch_multi_run(blur_multi* m, const T* src, T* dst, int nframes, int rows, int cols, int channels, int location, Body body)
+{
+    if (!m) return BLUR_ERR_INVALID;
+    if (nframes == 0) return BLUR_OK;
+    // frames queued by the caller on devices[0] must be complete before other devices (and other streams) read them
+    if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
+    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels * sizeof(T) : 0;
+    return blur_multi_run(m, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nframes, fb, location,
+                          [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) { return body(c, reinterpret_cast<const T*>(in), reinterpret_cast<T*>(out), n); });
+}
+
 template <typename T>
 static int blur_ch_multi(blur_multi* m, const T* src, T* dst, int nframes, int rows, int cols, int channels, double sigma, const blur_opts* opts, int location)
 {
     if (!m) return BLUR_ERR_INVALID;
     if (channels != 1 && channels != 3 && channels != 4) { m->err = "channels must be 1, 3 or 4"; return BLUR_ERR_INVALID; }
     if (!src || !dst || nframes < 0) { m->err = "null frame pointer or negative frame count"; return BLUR_ERR_INVALID; }
-    if (nframes == 0) return BLUR_OK;
-    // frames queued by the caller on devices[0] must be complete before other devices (and other streams) read them
-    if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
-    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels * sizeof(T) : 0;
-    return blur_multi_run(m, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nframes, fb, location,
-                          [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) {
-                              return blur_ch_batch_impl(c, reinterpret_cast<const T*>(in), reinterpret_cast<T*>(out), n, rows, cols, channels, sigma, opts);
-                          });
+    return blur_ch_multi_run(m, src, dst, nframes, rows, cols, channels, location,
+                             [=](blur_ctx* c, const T* in, T* out, int n) { return blur_ch_batch_impl(c, in, out, n, rows, cols, channels, sigma, opts); });
 }
 }  // extern "C++"
 
@@ -4442,15 +4442,9 @@ static int blur_ch_sigmas_multi(blur_multi* m, const T* src, T* dst, int nframes
     SigmaGroups sg;
     const char* why = nullptr;
     if (int rc = ch_sigmas_status(src, dst, nframes, rows, cols, channels, sigmas, sg, &why)) { if (m) m->err = why; return rc; }
-    if (!m) return BLUR_ERR_INVALID;
-    if (nframes == 0) return BLUR_OK;
-    if (location == 1 && (hipSetDevice(m->devices[0]) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { m->err = "hipDeviceSynchronize on the frames' device failed"; return BLUR_ERR_HIP; }
-    const size_t fb = rows > 0 && cols > 0 ? static_cast<size_t>(rows) * cols * channels * sizeof(T) : 0;
     const std::array<double, 4> sv = { sigmas[0], channels > 1 ? sigmas[1] : 0.0, channels > 2 ? sigmas[2] : 0.0, channels > 3 ? sigmas[3] : 0.0 };
-    return blur_multi_run(m, reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst), nframes, fb, location,
-                          [=](blur_ctx* c, const uint8_t* in, uint8_t* out, int n) {
-                              return blur_ch_sigmas_batch_impl(c, reinterpret_cast<const T*>(in), reinterpret_cast<T*>(out), n, rows, cols, channels, sv.data(), opts);
-                          });
+    return blur_ch_multi_run(m, src, dst, nframes, rows, cols, channels, location,
+                             [=](blur_ctx* c, const T* in, T* out, int n) { return blur_ch_sigmas_batch_impl(c, in, out, n, rows, cols, channels, sv.data(), opts); });
 }
 }  // extern "C++"
 
